@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """bench.py -- the RadixAttention serving hot path on MI355X.
 
-    python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1            # the plain run: set up, warm up, time the steps, one JSON line
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full     # + the side measurements listed below, after the timed region
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR   # + DIR/<name>.npy: what the last timed step returned
     python bench.py --gpus 8 --model llama-3-70b           # spawns the 8 ranks itself (headline TP=8 config)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
@@ -19,7 +21,15 @@ environment the script spawns its N ranks itself; it FAILS (never degrades) when
 it ends up with fewer ranks than asked, with eager decode where a hipGraph was
 asked for, or with another model than requested.
 
-The JSON line also carries
+A plain run does what `value` needs and nothing else: the line carries `value`, `ms_per_step` (milliseconds per timed step),
+the phase times of the timed steps and the rooflines computed from them.  `--dump-outputs DIR` writes, after the timed steps,
+the arrays the caller of the last timed step received (float64 / float32 .npy, rows in request order): `output_ids` [B, out]
+(every request's greedy tokens), `cached_tokens` [B] (radix hits) and `last_decode_logits` [rows, vocab] with
+`last_decode_logits_rows` (the logits of the step's last decode launch, as they stand in the decode graph's output buffer;
+a fixed seeded sample of the rows where all of them would pass 48 MB).  Prompts and weights are seeded: the same arguments
+give the same inputs in every run, so two builds compare output for output.
+
+With `--full` the JSON line also carries (each in a run of its own after the timed region; the --no-* switches drop single legs)
   roofline            the WHOLE decode step (one hipGraph replay) vs 8 TB/s, SURVEY section 8(d)'s bytes per step, `traffic` =
                       HBM bytes of one step from the committed PMC passes (= step_roofline, kept under its old key too)
   dominant_kernel_roofline / kernel_table
@@ -181,6 +191,13 @@ def parse_args():
     ap.add_argument("--operator-surface", action="store_true",
                     help="decode through the unfused per-operator hooks only (the path the sglang.srt registration "
                          "hooks reach without patching model classes)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the side measurements: per-kernel / attention / sampler rooflines, parity "
+                         "against the oracle, the CPU baseline, the job under the reference's Scheduler (the --no-* switches below "
+                         "drop single legs of it); off by default: a plain run only times the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one returned to DIR/<name>.npy (output_ids, cached_tokens, "
+                         "last_decode_logits + last_decode_logits_rows)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-kernel-roofline", action="store_true")
     ap.add_argument("--no-parity", action="store_true")
@@ -346,15 +363,18 @@ def worker(args):
         job(False)
     sync(); barrier()
     t_start = time.perf_counter()
-    hit_tokens = 0
+    hit_tokens, last_reqs = 0, []
     for _ in range(args.steps):
-        hit_tokens, _ = job(True)
+        hit_tokens, last_reqs = job(True)
     sync(); barrier()
     elapsed = time.perf_counter() - t_start
     if world > 1:
         t = torch.tensor([elapsed], device="cpu" if share_gpu else dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+
+    if args.dump_outputs and rank == 0 and last_reqs:
+        dump_outputs(Path(args.dump_outputs), runner, last_reqs)
 
     out_tokens = B * args.out * args.steps
     value = out_tokens / elapsed
@@ -428,7 +448,7 @@ def worker(args):
     }
 
     # ---- dominant hand-written kernels, measured live with HIP events on torch's stream ----
-    if rank == 0 and not args.no_kernel_roofline and not args.rank_of:
+    if args.full and rank == 0 and not args.no_kernel_roofline and not args.rank_of:
         try:
             result["pmc_record"] = {"file": PMC_NAME, "present": pmc is not None, "all_sources_current": pmc_current(pmc),
                                     "git_revision": pmc["stamp"].get("git_revision") if pmc else None}
@@ -437,7 +457,7 @@ def worker(args):
             result.setdefault("dominant_kernel_roofline", {"error": f"{type(e).__name__}: {e}"})
 
     # ---- parity of this very job against the oracle's plain torch ops on the GPU ----------
-    if rank == 0 and world == 1 and not args.no_parity and not kv_fp8 and not args.rank_of:
+    if args.full and rank == 0 and world == 1 and not args.no_parity and not kv_fp8 and not args.rank_of:
         try:
             from oracle.parity import teacher_forced_parity
 
@@ -476,14 +496,14 @@ def worker(args):
             result["parity"] = {"error": f"{type(e).__name__}: {e}"}
 
     # ---- CPU baseline: the oracle (reference torch-native path) on host cores --------------
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.rank_of:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline and not args.rank_of:
         try:
             result["cpu_baseline"] = cpu_baseline(args, cfg, runner, prompts)
         except Exception as e:
             result["cpu_baseline"] = {"error": f"{type(e).__name__}: {e}"}
 
     # ---- the same job under the REFERENCE'S scheduler with the plug-in (what a user of sglang gets) ------------------
-    if (rank == 0 and world == 1 and not args.no_reference_scheduler and not args.rank_of and not kv_fp8 and not reduced
+    if (args.full and rank == 0 and world == 1 and not args.no_reference_scheduler and not args.rank_of and not kv_fp8 and not reduced
             and not args.operator_surface and args.page_size == 1 and cfg.name == "llama-3-8b"):
         try:
             result["reference_scheduler"] = reference_scheduler_leg(args)
@@ -504,6 +524,31 @@ def worker(args):
         ps.destroy()
 
 
+DUMP_LOGITS_BYTES = 48 << 20   # of --dump-outputs' 64 MB: the float32 logits rows; the ids and hit counts are a few hundred KB
+
+
+def dump_outputs(out_dir, runner, reqs):
+    """--dump-outputs: the arrays the caller of the last timed step holds when it returns, read AFTER the timed region (nothing
+    is recorded inside it).  `reqs` are that step's requests in the running batch's order = the row order of the decode graph's
+    output buffer, which still holds the logits of the step's last decode launch; every array is written in request-id order."""
+    import numpy as np
+
+    out_dir.mkdir(parents=True, exist_ok=True)
+    order = sorted(range(len(reqs)), key=lambda i: reqs[i].rid)
+    np.save(out_dir / "output_ids.npy", np.asarray([reqs[i].output_ids for i in order], dtype=np.float64))
+    np.save(out_dir / "cached_tokens.npy", np.asarray([reqs[i].cached_tokens for i in order], dtype=np.float64))
+    gr = runner.graph_runner
+    if gr is None:                  # --no-graph: an eager step keeps no logits behind
+        return
+    bs = next(b for b in gr.capture_bs if b >= len(reqs))
+    logits = gr.outputs[bs][:len(reqs)]
+    keep = max(1, DUMP_LOGITS_BYTES // (logits.shape[-1] * 4))
+    rows = list(range(len(reqs))) if len(reqs) <= keep else sorted(random.Random(0).sample(range(len(reqs)), keep))
+    picked = torch.tensor([order[r] for r in rows], device=logits.device)
+    np.save(out_dir / "last_decode_logits.npy", logits[picked].float().cpu().numpy())
+    np.save(out_dir / "last_decode_logits_rows.npy", np.asarray(rows, dtype=np.float64))
+
+
 def reference_scheduler_leg(args):
     """BASELINE's job shape under the reference's OWN `Scheduler.run_event_loop()` (the server's default overlap loop), `ModelRunner`,
     `ScheduleBatch`, radix cache, allocator / pool classes from the platform factories and graph runner -- with this package loaded
@@ -518,8 +563,10 @@ def reference_scheduler_leg(args):
 
     script = ROOT / "tests" / "golden" / "ref_model.py"
     staged = ROOT / "oracle" / "_ref" / "sglang_model" / "sglang"
-    if not (staged.exists() or Path("/root/reference/python/sglang").exists()):
-        return {"skipped": "no staged reference sources (oracle/_ref/sglang_model): run __graft_entry__.build() where /root/reference exists"}
+    ref = os.environ.get("SGLANG_REFERENCE_ROOT")
+    if not (staged.exists() or (ref and os.access(os.path.join(ref, "python", "sglang"), os.R_OK))):
+        return {"skipped": "no staged reference sources (oracle/_ref/sglang_model): run __graft_entry__.build() with SGLANG_REFERENCE_ROOT "
+                           "naming a checkout of the reference"}
     job = f"{args.groups},{args.per_group},{args.prefix},{args.unique},{args.out}"
     out = Path(tempfile.mkdtemp(prefix="ref_sched_")) / "job.json"
     t0 = time.perf_counter()

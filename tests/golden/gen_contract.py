@@ -14,7 +14,8 @@ import ast
 import json
 from pathlib import Path
 
-REF = Path("/root/reference/python")
+# the reference's own checkout, named by SGLANG_REFERENCE_ROOT (where unset: a path that does not exist)
+REF = Path(__import__("os").environ.get("SGLANG_REFERENCE_ROOT") or Path(__file__).resolve().parent / "no_reference_checkout") / "python"
 OUT = Path(__file__).resolve().parent / "reference_contract.json"
 
 # module -> names to record ("Class.method" for methods, "Class" for the class record, "NAME" for constants)
@@ -173,7 +174,7 @@ def main():
         contract["modules"][rel[:-3].replace("/__init__", "").replace("/", ".")] = {
             "file": rel, "is_package": rel.endswith("__init__.py"), "names": extract(REF / rel, names)}
     for rel, names in KERNEL_NS.items():
-        contract["sgl_kernel"][rel] = extract(Path("/root/reference") / rel, names)
+        contract["sgl_kernel"][rel] = extract(REF.parent / rel, names)
     OUT.write_text(json.dumps(contract, indent=1, sort_keys=True))
     n = sum(len(m["names"]) for m in contract["modules"].values())
     print(f"wrote {OUT} ({n} names from {len(contract['modules'])} modules)")

@@ -27,7 +27,8 @@ from unittest import mock
 
 import torch
 
-REF = Path("/root/reference/python")
+# the reference's own checkout, named by SGLANG_REFERENCE_ROOT (where unset: a path that does not exist)
+REF = Path(__import__("os").environ.get("SGLANG_REFERENCE_ROOT") or Path(__file__).resolve().parent / "no_reference_checkout") / "python"
 OUT = Path(__file__).resolve().parent
 
 
@@ -667,7 +668,7 @@ def gen_llava_anyres():
 
 def main():
     if not REF.exists():
-        raise SystemExit("/root/reference not present: goldens can only be regenerated in the build container")
+        raise SystemExit("no reference checkout (SGLANG_REFERENCE_ROOT): goldens can only be regenerated from the reference's own sources")
     install_hook()
     if len(sys.argv) > 1 and sys.argv[1] == "--radix-live":            # --radix-live SEED STEPS VOCAB OUT: a fresh trace, pages 1 / 4 / 16
         gen_radix(seed_base=int(sys.argv[2]), steps=int(sys.argv[3]), pages=(1, 4, 16), vocab=int(sys.argv[4]), out=sys.argv[5])

@@ -6,14 +6,18 @@ express them, so `oracle/ops.py` restates them from the text of the reference's 
 This script pins that restatement: it imports the reference's `extend_attention_fwd` (extend_attention.py:753) and
 `decode_attention_fwd` (decode_attention.py:1163) themselves under triton-rocm and records their outputs.
 
-Two steps, because /root/reference does not exist on the GPU box:
+Two steps, because the reference's sources are not on the GPU machine:
 
-    python tests/golden/gen_triton_golden.py --stage      # build container: copies the four kernel files into
-                                                          # oracle/_ref/triton_ref/ (git-ignored, never committed,
-                                                          # travels with the gpurun snapshot)
-    gpurun -- python tests/golden/gen_triton_golden.py    # GPU box: writes gpurun_out/attention_triton.pt
-                                                          #          (+ --time: gpurun_out/r03_triton_ref_timing.json)
-    cp gpurun_out/attention_triton.pt tests/golden/       # committed fixture
+    python tests/golden/gen_triton_golden.py --stage      # where the reference is checked out: copies the four kernel
+                                                          # files into oracle/_ref/triton_ref/ (git-ignored, never
+                                                          # committed; it travels to the GPU machine with the tree)
+    python tests/golden/gen_triton_golden.py --out DIR/attention_triton.pt
+                                                          # on the MI355X: writes DIR/attention_triton.<case>.<part>.pt
+                                                          # (--time: the reference kernels' timings as JSON)
+    cp DIR/attention_triton.*.pt tests/golden/            # committed fixtures
+
+The cases are stored in parts (inputs / the four extend outputs / the verify and decode records) so that every committed
+file stays well under 1 MiB; `load_cases` below and the tests put a case's parts back into one dict.
 
 `sglang.srt.environ` / `sglang.srt.utils` are replaced by five-line shims (is_hip() -> True, env switches off);
 every line of arithmetic executed is the reference's.  Nothing under tests/ reads oracle/_ref at test time.
@@ -29,14 +33,15 @@ from pathlib import Path
 
 REPO = Path(__file__).resolve().parents[2]
 STAGE = REPO / "oracle" / "_ref" / "triton_ref"
-REF = Path("/root/reference/python")
+# the reference's own checkout, named by SGLANG_REFERENCE_ROOT (where unset: a path that does not exist)
+REF = Path(__import__("os").environ.get("SGLANG_REFERENCE_ROOT") or Path(__file__).resolve().parent / "no_reference_checkout") / "python"
 FILES = ["extend_attention.py", "decode_attention.py", "prefill_attention.py", "score_mod.py"]
 REL = Path("sglang/kernels/ops/attention")
 
 
 def stage() -> None:
     if not REF.exists():
-        raise SystemExit("/root/reference not present: staging only works in the build container")
+        raise SystemExit("no reference checkout (SGLANG_REFERENCE_ROOT): staging needs the reference's own sources")
     dst = STAGE / REL
     dst.mkdir(parents=True, exist_ok=True)
     for f in FILES:
@@ -214,9 +219,38 @@ def generate(out_path: Path) -> None:
 
     cases["_meta"] = dict(triton=triton.__version__, torch=str(torch.__version__), device=torch.cuda.get_device_name(0),
                           source="reference extend_attention_fwd / decode_attention_fwd, staged copies")
+    save_parts(torch, cases, out_path)
+
+
+def _part_of(key: str) -> str:
+    if key.startswith("out_extend_"):
+        return "out_extend"
+    return "verify" if key == "verify" or key.startswith(("out_verify", "out_decode")) else "inputs"
+
+
+def save_parts(torch, cases, out_path: Path) -> None:
+    """`out_path` = .../attention_triton.pt names the set: one file .../attention_triton.<case>.<part>.pt per case and part,
+    each {case: {the part's keys}}; `_meta` rides with every case's inputs."""
     out_path.parent.mkdir(parents=True, exist_ok=True)
-    torch.save(cases, out_path)
-    print("wrote", out_path, {k: len(v) for k, v in cases.items()})
+    for name, c in cases.items():
+        if name.startswith("_"):
+            continue
+        for part in ("inputs", "out_extend", "verify"):
+            blob = {name: {k: v for k, v in c.items() if _part_of(k) == part}}
+            if part == "inputs":
+                blob["_meta"] = cases["_meta"]
+            f = out_path.with_name(f"{out_path.stem}.{name}.{part}.pt")
+            torch.save(blob, f)
+            print("wrote", f, len(blob[name]), "keys,", f.stat().st_size, "bytes")
+
+
+def load_cases(torch, golden_dir: Path) -> dict:
+    """The parts of `save_parts` merged back: {case: {key: value}, "_meta": {...}}."""
+    cases = {}
+    for f in sorted(Path(golden_dir).glob("attention_triton.*.pt")):
+        for name, part in torch.load(f).items():
+            cases.setdefault(name, {}).update(part)
+    return cases
 
 
 def time_reference(out_path: Path) -> None:

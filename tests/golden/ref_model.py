@@ -48,11 +48,11 @@ _state = {}
 
 
 def ref_root():
-    """The container's checkout, else the staged copy, else None (REF_OBJECTS_ROOT forces a root: tests of the staged copy)."""
+    """The checkout SGLANG_REFERENCE_ROOT names, else the staged copy, else None (REF_OBJECTS_ROOT forces a root: tests of the staged copy)."""
     forced = os.environ.get("REF_OBJECTS_ROOT")
     if forced:
         return Path(forced) if (Path(forced) / "sglang").exists() else None
-    if (R.CONTAINER_REF / "sglang").exists():
+    if R.has_checkout():
         return R.CONTAINER_REF
     return STAGE if (STAGE / "sglang").exists() else None
 
@@ -2138,8 +2138,8 @@ def stage() -> None:
     with the gpurun snapshot)."""
     import shutil
 
-    if not (R.CONTAINER_REF / "sglang").exists():
-        raise SystemExit("/root/reference not present: staging only works in the build container")
+    if not R.has_checkout():
+        raise SystemExit("no reference checkout (SGLANG_REFERENCE_ROOT): staging needs the reference's own sources")
     files = set()
     for f in (R.CONTAINER_REF / "sglang").rglob("*.py"):
         rel = f.relative_to(R.CONTAINER_REF).as_posix()

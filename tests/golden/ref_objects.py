@@ -18,6 +18,7 @@ from __future__ import annotations
 
 import argparse
 import importlib
+import os
 import shutil
 import sys
 from contextlib import contextmanager
@@ -25,7 +26,9 @@ from pathlib import Path
 
 REPO = Path(__file__).resolve().parents[2]
 STAGE = REPO / "oracle" / "_ref" / "sglang_objects"
-CONTAINER_REF = Path("/root/reference/python")
+CONTAINER_REF = None        # the python/ directory of the reference's own checkout, where SGLANG_REFERENCE_ROOT names one
+if os.environ.get("SGLANG_REFERENCE_ROOT"):
+    CONTAINER_REF = Path(os.environ["SGLANG_REFERENCE_ROOT"]) / "python"
 MODULES = ["sglang.srt.utils.common", "sglang.srt.mem_cache.memory_pool", "sglang.srt.layers.radix_attention",
            "sglang.srt.model_executor.forward_batch_info", "sglang.srt.mem_cache.radix_cache", "sglang.srt.runtime_context",
            "sglang.kernels.fused_op", "sglang.srt.layers.layernorm", "sglang.srt.layers.rotary_embedding.base",
@@ -34,14 +37,22 @@ MODULES = ["sglang.srt.utils.common", "sglang.srt.mem_cache.memory_pool", "sglan
 _installed = {}
 
 
+def has_checkout() -> bool:
+    """A readable checkout of the reference named by SGLANG_REFERENCE_ROOT (unset, absent or unreadable: no)."""
+    try:
+        return CONTAINER_REF is not None and (CONTAINER_REF / "sglang").exists()
+    except OSError:
+        return False
+
+
 def ref_root():
-    """Where the reference sources can be imported from here: the container's checkout, else the staged copy, else None."""
+    """Where the reference sources can be imported from here: the checkout SGLANG_REFERENCE_ROOT names, else the staged copy, else None."""
     import os
 
     forced = os.environ.get("REF_OBJECTS_ROOT")          # tests of the staged copy inside the build container
     if forced:
         return Path(forced) if (Path(forced) / "sglang").exists() else None
-    if (CONTAINER_REF / "sglang").exists():
+    if has_checkout():
         return CONTAINER_REF
     if (STAGE / "sglang").exists():
         return STAGE
@@ -83,8 +94,8 @@ def single_rank(ns):
 
 
 def stage() -> None:
-    if not (CONTAINER_REF / "sglang").exists():
-        raise SystemExit("/root/reference not present: staging only works in the build container")
+    if not has_checkout():
+        raise SystemExit("no reference checkout (SGLANG_REFERENCE_ROOT): staging needs the reference's own sources")
     ns = install(CONTAINER_REF)
     failed = {name for name, _ in ns.hook.FAILED}
     files = []

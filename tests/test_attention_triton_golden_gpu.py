@@ -12,7 +12,11 @@ BF = torch.bfloat16
 
 
 def _cases(golden_dir):
-    cases = torch.load(golden_dir / "attention_triton.pt")
+    cases = {}          # stored in parts (tests/golden/gen_triton_golden.py save_parts): {case: {some of its keys}} per file
+    for f in sorted(golden_dir.glob("attention_triton.*.pt")):
+        for name, part in torch.load(f).items():
+            cases.setdefault(name, {}).update(part)
+    assert sorted(cases) == ["_meta", "gqa4_d128", "mha_d64"] and all(len(cases[k]) == 27 for k in ("gqa4_d128", "mha_d64")), sorted(cases)
     return {k: v for k, v in cases.items() if not k.startswith("_")}
 
 

@@ -169,11 +169,15 @@ def test_bruteforce_prefix_cache_matches_reference_trace(golden_dir):
 
 # --------------------------------------------------------------------------------------------------------------
 # Logit soft cap, custom (verify) mask and sliding window pinned against the REFERENCE'S OWN Triton kernels
-# (tests/golden/attention_triton.pt: outputs of extend_attention_fwd / decode_attention_fwd run under triton-rocm on an
+# (tests/golden/attention_triton.*.pt: outputs of extend_attention_fwd / decode_attention_fwd run under triton-rocm on an
 # MI355X by tests/golden/gen_triton_golden.py).  The Triton kernels round P to bf16 before the PV product and write
 # bf16, the oracle evaluates in fp32 and rounds once: the two agree to one bf16 ulp of the output.
 def _triton_cases(golden_dir):
-    cases = torch.load(golden_dir / "attention_triton.pt")
+    cases = {}          # stored in parts (tests/golden/gen_triton_golden.py save_parts): {case: {some of its keys}} per file
+    for f in sorted(golden_dir.glob("attention_triton.*.pt")):
+        for name, part in torch.load(f).items():
+            cases.setdefault(name, {}).update(part)
+    assert sorted(cases) == ["_meta", "gqa4_d128", "mha_d64"] and all(len(cases[k]) == 27 for k in ("gqa4_d128", "mha_d64")), sorted(cases)
     return {k: v for k, v in cases.items() if not k.startswith("_")}
 
 

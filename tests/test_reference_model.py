@@ -39,7 +39,7 @@ def _root_or_skip():
 
     root = ref_model.ref_root()
     if root is None:
-        pytest.skip("no reference sources here (neither /root/reference nor a staged copy)")
+        pytest.skip("no reference sources here (neither a checkout named by SGLANG_REFERENCE_ROOT nor a staged copy)")
     return root
 
 
