@@ -37,13 +37,96 @@ def timeit(fn, iters=24, warmup=3, reps=5):
     return s.elapsed_time(e) / (iters * reps) * 1e-3
 
 
+HBM_PEAK = 8.0e12            # MI355X_MICROARCH.md: HBM3E spec, bytes / s
+MFMA_PEAK = 2.5e15           # bf16 dense, flop / s
+
+# (model, projection, N = rows of w, K): Llama-3-8B, then one rank of eight of Llama-3-70B
+DENSE_TILED_SHAPES = [("8b", "qkv", 6144, 4096), ("8b", "o", 4096, 4096), ("8b", "gate_up", 28672, 4096),
+                      ("8b", "down", 4096, 14336), ("8b", "lm_head", 128256, 4096),
+                      ("70b/8", "qkv", 1280, 8192), ("70b/8", "o", 8192, 1024), ("70b/8", "gate_up", 7168, 8192),
+                      ("70b/8", "down", 8192, 3584)]
+
+
+def graph_of(fn, iters=24, warmup=3):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        for _ in range(iters):
+            fn()
+    g.replay()
+    torch.cuda.synchronize()
+    return g
+
+
+def dense_tiled_sweep(args):
+    """dense_tiled_gemm against the library path (F.linear, + the silu_and_mul kernel for the fused gate_up) at M = 256 and
+    512: both captured as graphs of 24 calls in one process, replayed alternately, 5 timed repetitions each (device
+    events); median, spread (max - min over the repetitions) and each path's share of the roofline bound
+    max(bytes / HBM peak, flops / bf16 MFMA peak), bytes and flops counted from the shapes."""
+    rows = []
+    iters, reps = 24, 5
+    for model, name, N, Kd in DENSE_TILED_SHAPES:
+        copies = max(2, int(600e6 // (N * Kd * 2)) + 1)     # rotate so the weights come from HBM, not the infinity cache
+        ws = [(torch.randn((N, Kd), device=DEV) * 0.02).to(BF) for _ in range(copies)]
+        it = [0]
+
+        def nxt():
+            it[0] = (it[0] + 1) % copies
+            return ws[it[0]]
+
+        for M in (256, 512):
+            x = torch.randn((M, Kd), device=DEV).to(BF)
+            for fused in ((False, True) if name == "gate_up" else (False,)):
+                n_out = N // 2 if fused else N
+                out = torch.empty((M, n_out), dtype=BF, device=DEV)
+                nbytes = (N * Kd + M * Kd + M * n_out) * 2
+                flops = 2 * M * N * Kd
+                t_hbm, t_mfma = nbytes / HBM_PEAK, flops / MFMA_PEAK
+                if fused:
+                    lib = graph_of(lambda: K.silu_and_mul(F.linear(x, nxt()), out=out), iters)
+                    new = graph_of(lambda: K.dense_tiled_gemm(x, nxt(), epilogue="silu_and_mul", out=out), iters)
+                else:
+                    lib = graph_of(lambda: F.linear(x, nxt()), iters)
+                    new = graph_of(lambda: K.dense_tiled_gemm(x, nxt(), out=out), iters)
+                times = {"library": [], "dense_tiled": []}
+                for _ in range(reps):
+                    for key, g in (("library", lib), ("dense_tiled", new)):
+                        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        s.record()
+                        g.replay()
+                        e.record()
+                        torch.cuda.synchronize()
+                        times[key].append(s.elapsed_time(e) / iters * 1e-3)
+                bn, sp = K.choose_dense_tiled_config(M, N, Kd, fused)
+                row = dict(model=model, shape=name, fused_silu=fused, M=M, N=N, K=Kd, block_n=bn, splits=sp,
+                           bound="hbm" if t_hbm >= t_mfma else "mfma", bound_us=max(t_hbm, t_mfma) * 1e6)
+                for key, ts in times.items():
+                    med = sorted(ts)[len(ts) // 2]
+                    row[key] = dict(median_us=med * 1e6, spread_us=(max(ts) - min(ts)) * 1e6, share_of_bound=max(t_hbm, t_mfma) / med)
+                row["dense_tiled_wins"] = (row["library"]["median_us"] - row["dense_tiled"]["median_us"]
+                                           > max(row["library"]["spread_us"], row["dense_tiled"]["spread_us"]))
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                del lib, new
+        del ws
+        torch.cuda.empty_cache()
+    if args.json:
+        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.json).write_text(json.dumps(rows, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
     ap.add_argument("--quick", action="store_true")
     ap.add_argument("--M", type=int, default=64)
     ap.add_argument("--blocked", action="store_true", help="chunk-major [K/128, M, 128] activations")
+    ap.add_argument("--dense-tiled", action="store_true", help="dense_tiled_gemm vs the library path at M = 256 / 512")
     args = ap.parse_args()
+    if args.dense_tiled:
+        return dense_tiled_sweep(args)
     shapes = [("gate_up", 28672, 4096), ("down", 4096, 14336), ("qkv", 6144, 4096), ("o", 4096, 4096),
               ("lm_head", 128256, 4096)]
     M = args.M

@@ -534,6 +534,24 @@ int sgl_amd_moe_tiled_gemm_ex(const void* a, const void* w, void* c, const int32
                               int64_t a_row_stride, int64_t w_row_stride, int64_t w_expert_stride, int64_t c_row_stride,
                               int64_t max_m_blocks, int fuse_silu, int out_f32, int align_block_m, int tile_rows, void* stream);
 
+/* ---- dense MFMA GEMM for tall decode batches (reference: srt/layers/linear.py:1596-1660 UnquantizedLinearMethod.apply;
+ *      epilogue 1: + srt/layers/activation.py:130 SiluAndMul) --------------------------------------------------------
+ * y[M, N] = x[M, K] . w[N, K]^T (+ bias) for sgl_amd_dense_tiled_gemm_min_rows() <= M <= ..._max_rows() (129..512, the rows
+ * past sgl_amd_wstream_gemm_max_rows()), bf16 in / out, fp32 accumulate; N %% 16 == 0, K %% 128 == 0, row-major x / y with
+ * any 16-byte (x, w) / 8-byte (y) aligned row stride.  A workgroup owns 256 rows x block_n (64 or 128) weight rows and one of
+ * num_k_splits contiguous K ranges, both operands staged through LDS by LDS-DMA, MFMA 16x16x32.  num_k_splits > 1 writes fp32
+ * partials [splits, M, N] to ws_partials (sgl_amd_dense_tiled_gemm_workspace_floats) and the combine kernel of
+ * sgl_amd_wstream_gemm sums them in split order: the result is a fixed function of (shape, block_n, num_k_splits).
+ *   epilogue 0: y[M, N]   = bf16(acc + bias)                      (bias may be NULL)
+ *   epilogue 1: y[M, N/2] = silu_and_mul of the [gate | up] rows of w (N = 2 I, I %% 16 == 0, no bias; activation.py:141-143
+ *               rounding); with one split it runs in the GEMM's own epilogue and the [M, N] intermediate is never written. */
+int sgl_amd_dense_tiled_gemm(const void* x, const void* w, const void* bias, void* y, int64_t M, int64_t N, int64_t K,
+                             int64_t x_row_stride, int64_t w_row_stride, int64_t y_row_stride, int epilogue, int block_n,
+                             int num_k_splits, void* ws_partials, void* stream);
+int sgl_amd_dense_tiled_gemm_min_rows(void);
+int sgl_amd_dense_tiled_gemm_max_rows(void);
+int64_t sgl_amd_dense_tiled_gemm_workspace_floats(int64_t M, int64_t N, int num_k_splits);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,6 +26,7 @@
 #include "common.hpp"
 #include "kv_format.hpp"
 #include "sglang_amd.h"
+#include "wstream_combine.hpp"
 
 using namespace sgl_amd;
 
@@ -724,6 +725,19 @@ int launch_nw(const WsParams& p, int nw, bool two_tiles, hipStream_t st, int row
 
 }  // namespace
 
+void sgl_amd::launch_wstream_combine(const float* part, const uint16_t* bias, uint16_t* y, int64_t y_row_stride,
+                                     int64_t y_chunk_stride, int M, int N, int splits, bool silu, hipStream_t stream) {
+  CombineParams c{};
+  c.part = part; c.bias = bias; c.y = y;
+  c.y_stride = y_row_stride; c.y_cstride = y_chunk_stride;
+  c.M = M; c.N = N; c.splits = splits;
+  if (silu) {
+    hipLaunchKernelGGL(wstream_combine_silu_kernel, dim3((N / 8 + 255) / 256, M), dim3(256), 0, stream, c);
+  } else {
+    hipLaunchKernelGGL(wstream_combine_kernel, dim3((N / 4 + 255) / 256, M), dim3(256), 0, stream, c);
+  }
+}
+
 static int g_ws_debug_flags = 0;
 
 extern "C" {
@@ -827,19 +841,17 @@ int sgl_amd_wstream_gemm(const void* x, const void* w, const void* bias, void* y
   if (int rc = wstream_launch_main("wstream_gemm", x, w, bias, y, M, N, K, x_row_stride, x_chunk_stride, w_row_stride, y_row_stride,
                                    y_chunk_stride, fused_silu, tiles_per_wave, combine, waves_per_group, num_k_splits, ws_partials, st))
     return rc;
-  if (combine) {
+  if (combine && epilogue != 2) {
+    launch_wstream_combine(static_cast<const float*>(ws_partials), static_cast<const uint16_t*>(bias), static_cast<uint16_t*>(y),
+                           y_row_stride, y_chunk_stride ? y_chunk_stride : 128, static_cast<int>(M), static_cast<int>(N),
+                           num_k_splits, epilogue == 1, st);
+  } else if (combine) {
     CombineParams c{};
     c.part = static_cast<const float*>(ws_partials); c.bias = static_cast<const uint16_t*>(bias); c.y = static_cast<uint16_t*>(y);
     c.residual = static_cast<uint16_t*>(residual); c.norm_w = static_cast<const uint16_t*>(norm_weight);
     c.y_stride = y_row_stride; c.y_cstride = y_chunk_stride ? y_chunk_stride : 128; c.res_stride = residual_row_stride;
     c.M = static_cast<int>(M); c.N = static_cast<int>(N); c.splits = num_k_splits; c.eps = eps;
-    if (epilogue == 0) {
-      hipLaunchKernelGGL(wstream_combine_kernel, dim3((c.N / 4 + 255) / 256, c.M), dim3(256), 0, st, c);
-    } else if (epilogue == 1) {
-      hipLaunchKernelGGL(wstream_combine_silu_kernel, dim3((c.N / 8 + 255) / 256, c.M), dim3(256), 0, st, c);
-    } else {
-      hipLaunchKernelGGL(wstream_combine_norm_kernel, dim3(c.M), dim3(kNormThreads), 0, st, c);
-    }
+    hipLaunchKernelGGL(wstream_combine_norm_kernel, dim3(c.M), dim3(kNormThreads), 0, st, c);
   }
   SGL_CHECK_LAUNCH("wstream_gemm");
   return 0;

@@ -115,7 +115,14 @@ class Linear(nn.Module):
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.streams(x):
             return kernels.wstream_gemm(x, self.weight.data, self.bias.data if self.bias is not None else None)
+        if self.tiles(x):
+            return kernels.dense_tiled_gemm(x, self.weight.data, self.bias.data if self.bias is not None else None)
         return F.linear(kernels.unblock(x), self.weight, self.bias)
+
+    def tiles(self, x: torch.Tensor, fused_silu: bool = False) -> bool:
+        """129..512 row-major rows where the dense MFMA tile GEMM measured ahead of the library."""
+        return (x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype == BF and self.weight.dtype == BF and x.stride(0) % 8 == 0
+                and kernels.dense_tiled_preferred(x.shape[0], self.weight.shape[0], self.weight.shape[1], fused_silu))
 
     def forward_all_reduce(self, x: torch.Tensor) -> torch.Tensor:
         """RowParallelLinear.forward (linear.py): all_reduce(self(x)); prefill-sized inputs overlap the collective with
@@ -161,6 +168,8 @@ class LlamaMLP(nn.Module):
         if not OPERATOR_SURFACE_ONLY and self.gate_up_proj.streams(x) and self.gate_up_proj.bias is None:
             return kernels.wstream_gemm(x, self.gate_up_proj.weight.data, epilogue="silu_and_mul",
                                         out_blocked=out_blocked and self.gate_up_proj.weight.shape[0] % 256 == 0)
+        if not OPERATOR_SURFACE_ONLY and self.gate_up_proj.bias is None and self.gate_up_proj.tiles(x, fused_silu=True):
+            return kernels.dense_tiled_gemm(x, self.gate_up_proj.weight.data, epilogue="silu_and_mul")
         return self.act_fn(self.gate_up_proj(x))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -397,6 +406,9 @@ class CausalLM(nn.Module):
             hidden_states = kernels.unblock(hidden_states)
         if hidden_states.is_cuda and kernels.wstream_preferred(rows, *self.lm_head.shape):
             logits = kernels.wstream_gemm(hidden_states, self.lm_head.data)
+        elif (hidden_states.is_cuda and hidden_states.dim() == 2 and hidden_states.stride(1) == 1 and hidden_states.stride(0) % 8 == 0
+              and hidden_states.dtype == BF and kernels.dense_tiled_preferred(rows, *self.lm_head.shape)):
+            logits = kernels.dense_tiled_gemm(hidden_states, self.lm_head.data)
         else:
             logits = F.linear(hidden_states, self.lm_head)
         logits = ps.tensor_model_parallel_all_gather(logits, dim=-1)

@@ -882,6 +882,83 @@ def wstream_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
     return out
 
 
+# ------------------------------------------------- dense MFMA GEMM for 129..512-row decode batches
+_DENSE_TILED_BLOCKS = (128, 64)         # wide first: at equal grid cover, the wide strip moves less activation traffic
+_DENSE_TILED_ROW_BLOCK = 256
+# (M, N, K) with "dense_tiled_wins" in profiles/dense_tiled_gemm_sweep.json
+_DENSE_TILED_WINS = frozenset({(256, 6144, 4096), (256, 4096, 14336), (512, 4096, 14336), (256, 1280, 8192), (512, 1280, 8192),
+                               (256, 7168, 8192), (256, 8192, 3584)})
+
+
+def dense_tiled_supported(M: int, N: int, K: int) -> bool:
+    return 128 < M <= 512 and N > 0 and N % 16 == 0 and K % 128 == 0 and K >= 128
+
+
+@functools.lru_cache(maxsize=None)
+def choose_dense_tiled_config(M: int, N: int, K: int, fused_silu: bool = False) -> Tuple[int, int]:
+    """(block_n, k_splits) for y[M,N] = x . w[N,K]^T (fused_silu: N counts the rows of w = 2 I, one pass, never split).
+    One workgroup is resident per CU, so column strips x row blocks x splits is paid for in whole rounds of the 256
+    CUs, and the smallest split count that fills its rounds wins: a round costs its K steps (fitted to the one-split
+    rows of profiles/dense_tiled_gemm_sweep.json: ~18 ns per K element for a wide tile, ~10.7 ns for a narrow one),
+    the whole walk never beats the weight bytes over ~5.5 TB/s, and split-K pays the fp32 partial round trip plus the
+    combine launch (the figures of choose_wstream_config).  Splits are bounded by the K chunks and by
+    splits * M * N * 4 <= N * K * 2: the partials never outweigh the weights."""
+    row_blocks = (M + _DENSE_TILED_ROW_BLOCK - 1) // _DENSE_TILED_ROW_BLOCK
+    chunks = K // 128
+    max_splits = 1 if fused_silu else max(1, min(chunks, K // (2 * M)))
+    best = None
+    for s in range(1, max_splits + 1):
+        for bn in _DENSE_TILED_BLOCKS:
+            strips = (N // 2 + bn // 2 - 1) // (bn // 2) if fused_silu else (N + bn - 1) // bn
+            rounds = (strips * row_blocks * s + _NUM_CUS - 1) // _NUM_CUS
+            steps = (chunks + s - 1) // s * 128
+            t = 2.0e-6 + max(rounds * steps * (18.0e-9 if bn == 128 else 10.7e-9), N * K * 2 / 5.5e12)
+            if s > 1:
+                t += 2 * s * M * N * 4 / 4e12 + 2.5e-6
+            if best is None or t < best[0]:
+                best = (t, bn, s)
+    return best[1], best[2]
+
+
+@functools.lru_cache(maxsize=None)
+def dense_tiled_preferred(M: int, N: int, K: int, fused_silu: bool = False) -> bool:
+    """Routing policy on top of dense_tiled_supported(): True only for the shapes where the kernel's median beat the
+    library path by more than the larger of the two spreads in profiles/dense_tiled_gemm_sweep.json
+    (benchmarks/gemm_sweep.py --dense-tiled, M = 256 and 512 only): e.g. 70B/8 qkv 20.3 vs 27.3 us at 256 rows, 27.0 vs
+    32.9 at 512; 8B down 52.9 vs 62.8 and 72.6 vs 90.1; 70B/8 unfused gate_up 60.0 vs 77.9 at 256.  Those are the
+    split-K shapes; the library keeps the one-pass ones (8B gate_up 143 vs 96 us at 512 rows, lm_head 548 vs 505) and
+    every fused-silu shape (75-138 vs 73-106 us), and everything that was not measured."""
+    return not fused_silu and dense_tiled_supported(M, N, K) and (M, N, K) in _DENSE_TILED_WINS
+
+
+def dense_tiled_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: str = "none",
+                     out: Optional[torch.Tensor] = None, block_n: Optional[int] = None,
+                     splits: Optional[int] = None) -> torch.Tensor:
+    """F.linear(x, w, bias) for 129..512 rows on the dense MFMA tile kernel; epilogue="silu_and_mul": w is [2 I, K]
+    (gate rows, then up rows) and the result is silu(gate) * up [M, I] (in the GEMM's own epilogue with one split,
+    in the split-K combine kernel otherwise).  x and out are row-major with any aligned row stride."""
+    _dev(x, w)
+    _need(x.dtype == _BF16 and w.dtype == _BF16 and x.dim() == 2 and w.dim() == 2, "dense_tiled_gemm: bf16 2-D x / w")
+    _need(epilogue in ("none", "silu_and_mul"), "dense_tiled_gemm: epilogue is 'none' or 'silu_and_mul'")
+    M, K = x.shape
+    N = w.shape[0]
+    _need(w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1, "dense_tiled_gemm: shapes / contiguity")
+    _need(bias is None or (bias.dtype == _BF16 and bias.shape == (N,) and bias.is_contiguous()), "dense_tiled_gemm: bias is bf16 [N]")
+    ep = _WS_EPILOGUES[epilogue]
+    n_out = N // 2 if ep == 1 else N
+    if out is None:
+        out = torch.empty((M, n_out), dtype=_BF16, device=x.device)
+    _need(out.dtype == _BF16 and out.shape == (M, n_out) and out.stride(1) == 1, "dense_tiled_gemm: out is bf16 [M, N] rows")
+    if block_n is None or splits is None:
+        bn_auto, s_auto = choose_dense_tiled_config(M, N, K, ep == 1 and splits in (None, 1))
+    bn = block_n or bn_auto
+    s = splits or s_auto
+    ws = _gemm_workspace(x.device, native.lib().sgl_amd_dense_tiled_gemm_workspace_floats(M, N, s)) if s > 1 else None
+    native.call("sgl_amd_dense_tiled_gemm", x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, x.stride(0),
+                w.stride(0), out.stride(0), ep, bn, s, _ptr(ws), _stream())
+    return out
+
+
 def wstream_qkv_rope(x: torch.Tensor, w_qkv: torch.Tensor, bias: Optional[torch.Tensor], positions: torch.Tensor,
                      cos_sin_cache: torch.Tensor, num_q_heads: int, num_kv_heads: int, head_dim: int,
                      k_cache: torch.Tensor, v_cache: torch.Tensor, cache_loc: torch.Tensor,
