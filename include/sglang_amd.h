@@ -275,6 +275,27 @@ int sgl_amd_top_k_top_p_min_p_sample_from_logits(const void* logits, int logits_
                                                  const int64_t* seeds, const int64_t* positions, int32_t* out_ids,
                                                  void* ws_keys, void* ws_toks, int32_t* out_n_keep, int num_splits,
                                                  void* ws_fast, void* stream);
+/* Log-probabilities straight from the logits (srt/layers/sampler.py:143-146, 237-271 and the reference's get_top_logprobs /
+ * get_token_ids_logprobs: log_softmax or log(probs) over [batch, vocab], logprobs.topk, a gather per request) in two launches that
+ * never write a [batch, vocab] matrix.  logits bf16 or fp32, row stride >= vocab (vector loads for rows that are 8-byte (bf16) /
+ * 16-byte (fp32) aligned, element loads otherwise).  logprob(j) = z_j - lse, z = x / temperatures[b] (one correctly rounded fp32
+ * division; temperatures NULL: z = x, the greedy branch's log_softmax(logits)), lse from (max, sum) partials of num_splits column
+ * ranges merged in range order (deterministic).  Outputs:
+ *   chosen_logprob[b] = logprob(ids[b]); ids int32 (ids_is_int64 = 0) or int64, possibly written by an earlier launch on the
+ *     stream, NULL to skip; an id outside [0, vocab) is not dereferenced, its entry is NaN;
+ *   top_idx[b, :] = the n_top columns ordered by (raw logit descending, column ascending) -- NaN as in sgl_amd_argmax, -inf
+ *     behind every finite value -- and top_val[b, :] their log-probabilities; rows shorter than n_top end in (-1, -inf);
+ *     0 <= n_top <= sgl_amd_logprobs_max_top();
+ *   req_val[i] = logprob(req_ids[i]) for the row b with req_offsets[b] <= i < req_offsets[b + 1] (CSR; req_offsets int32
+ *     [batch + 1], req_total = req_offsets[batch]; either pointer NULL: no listed ids).
+ * num_splits: 1..64; workspace: caller-owned, sgl_amd_logprobs_workspace_bytes(batch, num_splits, n_top) bytes, 8-byte aligned,
+ * no initial state.  batch <= 65535, vocab < 2^31. */
+int sgl_amd_logprobs_max_top(void);
+int64_t sgl_amd_logprobs_workspace_bytes(int64_t batch, int num_splits, int n_top);
+int sgl_amd_logprobs_from_logits(const void* logits, int logits_is_bf16, int64_t row_stride, const float* temperatures, const void* ids,
+                                 int ids_is_int64, int64_t batch, int64_t vocab, int n_top, const int32_t* req_offsets,
+                                 const int32_t* req_ids, int64_t req_total, float* chosen_logprob, float* top_val, int32_t* top_idx,
+                                 float* req_val, int num_splits, void* workspace, void* stream);
 /* sgl_kernel.top_k_renorm_prob / top_p_renorm_prob (kernels/aot/python/sgl_kernel/sampling.py:28,79)
  * and sampler.py:753-762 top_p_normalize_probs_torch: zero everything outside the kept sorted
  * prefix and renormalise.  Per-row arrays override the scalar values when non-NULL;

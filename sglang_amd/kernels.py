@@ -637,6 +637,69 @@ def sample_from_bf16_logits(logits: torch.Tensor, *args, **kwargs):
     return sample_from_logits(logits, *args, **kwargs) if logits.dtype == _BF16 else None
 
 
+def logprobs_max_top() -> int:
+    return native.lib().sgl_amd_logprobs_max_top()
+
+
+def logprob_ranges(batch: int, vocab: int, n_top: int) -> int:
+    """Column ranges per row for logprobs_from_logits: the softmax's count (about 2048 workgroups over the chip), one range for
+    rows shorter than a range's worth of columns; with top lists never below what keeps a range inside one 8192-column register
+    burst nor above ~1024 candidate pairs per row for the finish launch."""
+    splits = min(64, 2048 // max(1, batch))
+    if splits < 2 or vocab < 4096 * splits // 8:
+        return 1
+    if n_top > 0:
+        splits = min(splits, max(1024 // n_top, min(64, -(-vocab // 8192))))
+    return splits
+
+
+def logprobs_from_logits(logits: torch.Tensor, temperatures: Optional[torch.Tensor], ids: Optional[torch.Tensor], n_top: int = 0,
+                         token_ids=None):
+    """sampler.py:143-146, 237-271 + get_top_logprobs / get_token_ids_logprobs straight from the logits (sampling_logprobs.hip: two
+    launches, no [B, V] intermediate).  logits bf16 / fp32 [B, V]; temperatures fp32 [B] (or [B, 1]), None = no division (the greedy
+    branch's log_softmax(logits)); ids [B] int32 / int64, the chosen tokens (None: skipped); token_ids: a list of per-row lists or None.
+    Returns (chosen fp32 [B] | None, top_val fp32 [B, n_top], top_idx int32 [B, n_top], req_val fp32 [total] | None): top_idx is
+    ordered by (raw logit descending, column ascending) and ends in (-1, -inf) pairs when V < n_top; req_val is the rows' lists
+    back to back.  A token whose fp32 probability underflows still gets its finite log-probability.  (The listed ids are
+    validated and uploaded from the host: pass token_ids=None under graph capture.)"""
+    _dev(logits, temperatures, ids)
+    _need(logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype in (torch.float32, _BF16), "logprobs: fp32 or bf16 [B, V] row-major logits")
+    B, V = logits.shape
+    _need(1 <= B <= 65535 and 1 <= V < 2 ** 31, "logprobs: 1 <= B <= 65535, 1 <= V < 2^31")
+    _need(0 <= n_top <= logprobs_max_top(), f"logprobs: n_top must be in [0, {logprobs_max_top()}]")
+    dev = logits.device
+    t = None
+    if temperatures is not None:
+        t = temperatures.reshape(-1)
+        _need(t.dtype == torch.float32 and t.numel() == B and t.is_contiguous(), "logprobs: temperatures [B] fp32")
+    if ids is not None:
+        _need(ids.dtype in (torch.int32, torch.int64) and ids.shape == (B,) and ids.is_contiguous(), "logprobs: ids int32 / int64 [B]")
+    offsets = req = req_val = None
+    total = 0
+    if token_ids is not None and any(r is not None for r in token_ids):
+        _need(len(token_ids) == B, "logprobs: token_ids needs one entry per row")
+        flat, offs = [], [0]
+        for r in token_ids:
+            for i in (r or ()):
+                _need(0 <= int(i) < V, f"logprobs: listed token id {i} outside [0, {V})")
+                flat.append(int(i))
+            offs.append(len(flat))
+        total = len(flat)
+        csr = torch.tensor(offs + flat, dtype=torch.int32).to(dev, non_blocking=True)
+        offsets, req = csr[:B + 1], csr[B + 1:]
+        req_val = torch.empty(total, dtype=torch.float32, device=dev)
+    chosen = torch.empty(B, dtype=torch.float32, device=dev) if ids is not None else None
+    top_val = torch.empty((B, n_top), dtype=torch.float32, device=dev)
+    top_idx = torch.empty((B, n_top), dtype=torch.int32, device=dev)
+    splits = logprob_ranges(B, V, n_top)
+    # (allocated per call: under graph capture it comes from the graph's pool like every other intermediate)
+    ws = torch.empty(native.lib().sgl_amd_logprobs_workspace_bytes(B, splits, n_top) // 8, dtype=torch.int64, device=dev)
+    native.call("sgl_amd_logprobs_from_logits", logits.data_ptr(), 1 if logits.dtype == _BF16 else 0, logits.stride(0), _ptr(t), _ptr(ids),
+                1 if ids is not None and ids.dtype == torch.int64 else 0, B, V, n_top, _ptr(offsets), _ptr(req), total, _ptr(chosen),
+                top_val.data_ptr() if n_top else None, top_idx.data_ptr() if n_top else None, _ptr(req_val), splits, ws.data_ptr(), _stream())
+    return chosen, top_val, top_idx, req_val
+
+
 def _renorm(probs: torch.Tensor, top_k, top_p) -> torch.Tensor:
     _dev(probs)
     probs = probs.float()

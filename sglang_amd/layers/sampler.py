@@ -54,8 +54,8 @@ class LogitsProcessorOutput:
     next_token_token_ids_logprobs_idx: Optional[List] = None
 
 
-# which route the non-greedy batches of this process took (tests / telemetry: tests/golden/ref_model.py reports it)
-served = {"one_call_from_logits": 0, "softmax_then_sample": 0}
+# which route the non-greedy batches, and the return_logprob calls, of this process took (tests / telemetry: tests/golden/ref_model.py reports it)
+served = {"one_call_from_logits": 0, "softmax_then_sample": 0, "logprobs_from_logits": 0, "logprobs_full_matrix": 0}
 
 
 class Sampler(nn.Module):
@@ -77,9 +77,13 @@ class Sampler(nn.Module):
         if pre is not None:
             logits = pre(logits, sampling_info)
         logprobs = None
+        # return_logprob, standalone (no output_logprob_processor bound: that interface needs the full matrix): the logprob outputs
+        # come from ONE pass over the logits (kernels.logprobs_from_logits), whenever the logits survive the sampling call
+        from_logits = return_logprob and self._logprobs_from_logits_ok(top_logprobs_nums)
+        src, src_temperatures = logits, None           # what the logprob kernel reads: the logits as handed in
         if sampling_info.is_all_greedy:
             ids = kernels.argmax(logits)                                    # sampler.py:133-141
-            if return_logprob:
+            if return_logprob and not from_logits:
                 logprobs = torch.log_softmax(logits.float(), dim=-1)        # :143-146
         else:
             # sampler.py:148-152, 211-260: div_ temperature, softmax in place, then sample from probs
@@ -87,17 +91,20 @@ class Sampler(nn.Module):
                                         or sampling_info.need_min_p_sampling)
             probs = ids = None
             min_ps = sampling_info.min_ps if sampling_info.need_min_p_sampling else None
-            if not return_logprob:
-                # The logits of a decode-sized batch (bf16, or the fp32 the reference's LogitsProcessor hands over), no logprobs asked
-                # for.  Filtered sampling: ONE native call, the probabilities are never written (and the logits not overwritten with
-                # them: sampler.py:216 does that in place, nothing downstream reads them without return_logprob); otherwise bf16
-                # logits are widened inside the softmax launches (exact; no separate pass)
+            src_temperatures = sampling_info.temperatures
+            if not return_logprob or from_logits:
+                # The logits of a decode-sized batch (bf16, or the fp32 the reference's LogitsProcessor hands over).  Filtered sampling:
+                # ONE native call, the probabilities are never written (and the logits not overwritten with them: sampler.py:216 does
+                # that in place; the logprob kernel reads the untouched logits afterwards); otherwise bf16 logits are widened inside the
+                # softmax launches (exact; no separate pass)
                 if not simple_sampling_case:
                     ids = kernels.sample_from_logits(logits, sampling_info.temperatures, sampling_info.top_ks, sampling_info.top_ps,
                                                      min_ps, sampling_info.sampling_seed, positions)
                     served["one_call_from_logits" if ids is not None else "softmax_then_sample"] += 1
                 if ids is None and logits.dtype == torch.bfloat16:
                     probs = kernels.softmax_temperature_from_bf16(logits, sampling_info.temperatures)
+            # the in-place fp32 softmax overwrites fp32 logits before the ids exist: those calls keep the log(probs) route
+            from_logits = from_logits and (ids is not None or src.dtype == torch.bfloat16)
             if ids is None:
                 if probs is None:
                     if logits.dtype != torch.float32:
@@ -109,12 +116,42 @@ class Sampler(nn.Module):
                 else:
                     ids = kernels.top_k_top_p_min_p_sample(probs, sampling_info.top_ks, sampling_info.top_ps, min_ps,
                                                            sampling_info.sampling_seed, positions)
-            if return_logprob:
+            if return_logprob and not from_logits:
                 logprobs = torch.log(probs)                                 # :252-257
         if return_logprob:
-            self._write_logprobs(logits_output, logprobs, ids, top_logprobs_nums, token_ids_logprobs)
+            served["logprobs_from_logits" if from_logits else "logprobs_full_matrix"] += 1
+            if from_logits:
+                self._write_logprobs_from_logits(logits_output, src, src_temperatures, ids, top_logprobs_nums, token_ids_logprobs)
+            else:
+                self._write_logprobs(logits_output, logprobs, ids, top_logprobs_nums, token_ids_logprobs)
         self._sync_token_ids_across_tp(ids, sampling_info)     # in place, like the reference's (returns None there)
         return ids
+
+    def _logprobs_from_logits_ok(self, top_logprobs_nums) -> bool:
+        """The logprob kernel serves the standalone sampler with top lists up to its compile-time cap; bound to a reference Sampler
+        the instance's output_logprob_processor is handed the full matrix as before."""
+        return (getattr(self, "output_logprob_processor", None) is None
+                and max(top_logprobs_nums or [0]) <= kernels.logprobs_max_top())
+
+    def _write_logprobs_from_logits(self, logits_output, logits, temperatures, ids, top_logprobs_nums, token_ids_logprobs) -> None:
+        """The five logprob fields of _write_logprobs (same types and shapes) from kernels.logprobs_from_logits: no [B, V]
+        log-probability matrix, no topk over it.  The one intended difference: a token whose probability underflows in fp32 gets
+        its finite log-probability (z - logsumexp(z)) where log(probs) gave -inf."""
+        k = max(top_logprobs_nums) if top_logprobs_nums else 0
+        chosen, top_val, top_idx, req_val = kernels.logprobs_from_logits(logits, temperatures, ids, k, token_ids_logprobs)
+        logits_output.next_token_logprobs = chosen
+        if k > 0:
+            vals, idx = top_val.tolist(), top_idx.tolist()
+            logits_output.next_token_top_logprobs_val = [v[:n] for v, n in zip(vals, top_logprobs_nums)]
+            logits_output.next_token_top_logprobs_idx = [i[:n] for i, n in zip(idx, top_logprobs_nums)]
+        if token_ids_logprobs and any(t is not None for t in token_ids_logprobs):
+            flat, at, out = req_val.tolist(), 0, []
+            for t in token_ids_logprobs:
+                n = len(t) if t is not None else 0
+                out.append(flat[at:at + n])
+                at += n
+            logits_output.next_token_token_ids_logprobs_val = out
+            logits_output.next_token_token_ids_logprobs_idx = [list(t) if t is not None else [] for t in token_ids_logprobs]
 
     def _write_logprobs(self, logits_output, logprobs, ids, top_logprobs_nums, token_ids_logprobs) -> None:
         """sampler.py:262-271: bound to a reference Sampler the instance's own output_logprob_processor does it;
