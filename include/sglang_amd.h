@@ -517,6 +517,33 @@ int sgl_amd_extend_attention_ex(const void* q, void* out, const void* k_cache, c
                                 int causal, int kv_fp8, float k_scale, float v_scale, int page_size, int kv_layout_hnd,
                                 int sliding_window, float logit_cap, const void* custom_mask, const int64_t* mask_indptr, int skip_prefix_custom_mask,
                                 void* stream);
+/* Split-KV short-extend ("tree verify") attention: the TARGET_VERIFY step of speculative decoding (triton_backend.py:860-919;
+ * extend_attention.py USE_CUSTOM_MASK with skip_prefix_custom_mask = 1), shaped like a decode kernel.  Same meaning as
+ * sgl_amd_extend_attention_ex, restricted: q / out [total_tokens, H_q, D] bf16 with token strides in elements (q may be a view
+ * into the qkv projection), D in {64, 128}; bf16 token-major pools [slots, H_kv, D] addressed through
+ * req_to_token[req_pool_indices[b], t] (any page size: slot addressing is the same); no fp8 / head-major pools, sliding window
+ * or logit cap -- those stay on the extend kernel.  Request b owns query tokens qo_indptr[b]..qo_indptr[b + 1] (e_b of them),
+ * has prefix_lens[b] cached tokens and seq_lens[b] = prefix_lens[b] + e_b; the new K/V rows are already in the pool.  Query i
+ * sees every position < prefix_lens[b], and position prefix_lens[b] + j when
+ * custom_mask[mask_indptr[b] + i * seq_lens[b] + prefix_lens[b] + j] != 0 (request b's [e_b, seq_lens[b]] row-major uint8
+ * block; the bytes under the prefix columns are never read); custom_mask NULL (with mask_indptr NULL): j <= i, the causal
+ * rule of a plain short extend.  Every query must see at least one position (a query that sees none gets zeros).
+ * The (query token, q head of the GQA group) pairs of one (request, kv head) share a workgroup:
+ * max_extend_len * (H_q / H_kv) <= sgl_amd_verify_attention_max_rows() (64), anything larger returns -1.
+ * Grid = (num_splits, H_kv, batch): split s of request b covers a contiguous run of whole 64-token tiles of [0, seq_lens[b]),
+ * computed on the device from the step's own lengths (graph-safe: the grid never depends on them); num_splits 1..64 is the
+ * caller's choice.  num_splits == 1 writes `out` directly and needs no workspace; otherwise fp32 partials go to the
+ * caller-owned ws_acc [total_tokens, H_q, num_splits, D] and ws_ml [total_tokens, H_q, num_splits, 2] (no initial state)
+ * and a second launch sums them in split order: the result is a fixed function of (inputs, num_splits).  Every token in
+ * [0, total_tokens) must belong to a request. */
+int sgl_amd_verify_attention_max_rows(void);
+int sgl_amd_verify_attention(const void* q, void* out, const void* k_cache, const void* v_cache, const int32_t* req_to_token,
+                             int64_t req_to_token_stride, const int64_t* req_pool_indices, const int32_t* seq_lens,
+                             const int32_t* prefix_lens, const int32_t* qo_indptr, int64_t batch, int64_t total_tokens,
+                             int max_extend_len, int num_q_heads, int num_kv_heads, int head_dim, int64_t q_token_stride,
+                             int64_t out_token_stride, int64_t k_cache_row_stride, int64_t v_cache_row_stride, float sm_scale,
+                             const void* custom_mask, const int64_t* mask_indptr, int num_splits, float* ws_acc, float* ws_ml,
+                             void* stream);
 /* Test / tuning override of the extend kernel's workgroup shape (process-wide; the library never reads the
  * environment): shape 0 = automatic, 41 / 42 / 82 = waves x 16-row tiles per wave (rows per workgroup 64 / 128 / 256);
  * flags bit 0 keeps bf16 8-wave launches on the general single-image kernel, bit 1 sends them to the ping-pong

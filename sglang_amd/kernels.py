@@ -344,6 +344,84 @@ def extend_attention(q: torch.Tensor, out: torch.Tensor, k_cache: torch.Tensor, 
     return out
 
 
+# ------------------------------------------------------ split-KV tree-verify (short-extend) attention
+VERIFY_MAX_SPLITS = 32      # workspace cap: fp32 partials of [tokens, Hq, splits, D]
+_VERIFY_TILE = 64
+
+
+def verify_attention_max_rows() -> int:
+    return native.lib().sgl_amd_verify_attention_max_rows()
+
+
+def verify_attention_supported(max_extend_len: int, group: int, head_dim: int, opt: Optional[dict] = None) -> bool:
+    """What verify_attention.hip serves: bf16 token-major pools, no window / cap, head dim 64 / 128, and all
+    (query token, q head of the group) pairs of a request in one workgroup.  `opt`: the extend call's keyword options."""
+    opt = opt or {}
+    if opt.get("kv_fp8") or opt.get("hnd") or opt.get("sliding_window", -1) >= 0 or opt.get("logit_cap", 0.0) > 0:
+        return False
+    return head_dim in (64, 128) and 0 < max_extend_len * group <= verify_attention_max_rows()
+
+
+def choose_verify_splits(batch: int, num_kv_heads: int, max_len: int) -> int:
+    """Static split count: about two workgroups per CU, every split at least one 64-token tile, at most VERIFY_MAX_SPLITS."""
+    blocks = max(1, batch * num_kv_heads)
+    want = (2 * _NUM_CUS + blocks - 1) // blocks
+    return max(1, min(want, max_len // _VERIFY_TILE, VERIFY_MAX_SPLITS))
+
+
+# Measured on an MI355X against extend_attention with the same tree mask (benchmarks/verify_attention_time.py,
+# profiles/verify_attention_time.json: Llama-3-8B and 70B / 8 head geometries, B 1 / 16 / 64, 4 / 8 / 16 draft tokens, contexts
+# 1024 / 4096 / 16384, cold pools): the split-KV kernel is ahead in every supported cell, 1.5x (B 16, 16 draft tokens, 1024) to
+# 28x (B 1, 16384), always by at least 39 x the run-to-run spread.  Contexts below the shortest one measured stay where they were.
+VERIFY_MIN_CONTEXT = 1024
+
+
+def verify_attention_preferred(batch: int, num_kv_heads: int, max_extend_len: int, group: int, max_len: int) -> bool:
+    """Routing policy of HipAttnBackend.forward_extend for TARGET_VERIFY batches: the measured region (see VERIFY_MIN_CONTEXT).
+    `max_len` is the context bound the splits are chosen for: the pool's context length under capture."""
+    return max_len >= VERIFY_MIN_CONTEXT
+
+
+def verify_workspace(total_tokens: int, num_q_heads: int, head_dim: int, num_splits: int, device) -> Tuple[torch.Tensor, torch.Tensor]:
+    acc = torch.empty((total_tokens, num_q_heads, num_splits, head_dim), dtype=torch.float32, device=device)
+    ml = torch.empty((total_tokens, num_q_heads, num_splits, 2), dtype=torch.float32, device=device)
+    return acc, ml
+
+
+def verify_attention(q: torch.Tensor, out: torch.Tensor, k_cache: torch.Tensor, v_cache: torch.Tensor,
+                     req_to_token: torch.Tensor, req_pool_indices: torch.Tensor, seq_lens: torch.Tensor,
+                     prefix_lens: torch.Tensor, qo_indptr: torch.Tensor, max_extend_len: int, sm_scale: float,
+                     custom_mask: Optional[torch.Tensor] = None, mask_indptr: Optional[torch.Tensor] = None,
+                     num_splits: int = 1, ws_acc: Optional[torch.Tensor] = None, ws_ml: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """q/out [T, Hq, D] (q may be a strided view); k_cache/v_cache bf16 [slots, Hkv, D]; int32 seq_lens / prefix_lens /
+    qo_indptr; custom_mask uint8 / bool flat with int64 mask_indptr [B + 1] (the prefix columns are not consulted), or None for
+    the causal rule; ws_acc [>= T, Hq, num_splits, D] / ws_ml [>= T, Hq, num_splits, 2] fp32 when num_splits > 1."""
+    _dev(q, out, k_cache, v_cache, req_to_token, req_pool_indices, seq_lens, prefix_lens, qo_indptr)
+    T, Hq, D = q.shape
+    Hkv = k_cache.shape[1]
+    _need(q.dtype == _BF16 and k_cache.dtype == _BF16 and v_cache.dtype == _BF16 and out.dtype == _BF16, "verify_attention: bf16 only")
+    _need(seq_lens.dtype == torch.int32 and prefix_lens.dtype == torch.int32 and qo_indptr.dtype == torch.int32, "verify_attention: int32 lens")
+    _need(req_pool_indices.dtype == torch.int64 and req_to_token.dtype == torch.int32, "verify_attention: index dtypes")
+    _need(q.stride(2) == 1 and q.stride(1) == D and out.stride(2) == 1 and out.stride(1) == D, "verify_attention: q/out head layout")
+    _need(k_cache.stride(2) == 1 and k_cache.stride(1) == D and v_cache.stride(2) == 1 and v_cache.stride(1) == D, "verify_attention: cache layout")
+    if custom_mask is not None:
+        _dev(custom_mask, mask_indptr)
+        custom_mask = custom_mask.view(torch.uint8) if custom_mask.dtype == torch.bool else custom_mask
+        _need(custom_mask.dtype == torch.uint8 and custom_mask.is_contiguous() and mask_indptr is not None
+              and mask_indptr.dtype == torch.int64, "verify_attention: uint8 custom_mask + int64 mask_indptr")
+    if num_splits > 1 and ws_acc is not None and ws_ml is not None:
+        _dev(ws_acc, ws_ml)
+        _need(ws_acc.dtype == torch.float32 and ws_ml.dtype == torch.float32 and ws_acc.is_contiguous() and ws_ml.is_contiguous()
+              and ws_acc.numel() >= T * Hq * num_splits * D and ws_ml.numel() >= T * Hq * num_splits * 2,
+              "verify_attention: fp32 workspaces of [T, Hq, num_splits, D] and [T, Hq, num_splits, 2]")
+    native.call("sgl_amd_verify_attention", q.data_ptr(), out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                req_to_token.data_ptr(), req_to_token.stride(0), req_pool_indices.data_ptr(), seq_lens.data_ptr(),
+                prefix_lens.data_ptr(), qo_indptr.data_ptr(), seq_lens.numel(), T, int(max_extend_len), Hq, Hkv, D,
+                q.stride(0), out.stride(0), k_cache.stride(0), v_cache.stride(0), float(sm_scale),
+                _ptr(custom_mask), _ptr(mask_indptr) if custom_mask is not None else None, int(num_splits),
+                _ptr(ws_acc), _ptr(ws_ml), _stream())
+    return out
+
 
 # ------------------------------------------------------------- shared-prefix (cascade) decode
 CASCADE_MIN_SHARED = 128

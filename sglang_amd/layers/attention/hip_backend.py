@@ -53,6 +53,7 @@ class _Meta:
     cascade: Optional["kernels.CascadeWorkspace"] = None   # shared-prefix decode plan + split slots
     mask_indptr: Optional[torch.Tensor] = None             # TARGET_VERIFY: offsets of the requests' blocks in the flat mask
     verify_mask: Optional[torch.Tensor] = None             # TARGET_VERIFY: the persistent copy of this step's flat tree mask
+    verify_splits: int = 0                                 # TARGET_VERIFY: > 0 routes to the split-KV verify kernel with that many splits
 
 
 def choose_num_splits(batch: int, num_kv_heads: int, group: int, max_len: int, target_blocks: int = 512) -> int:
@@ -123,6 +124,17 @@ def cascade_wanted(model_runner) -> bool:
     return bool(wanted)
 
 
+def verify_kernel_wanted(model_runner) -> Optional[bool]:
+    """Split-KV verify kernel for TARGET_VERIFY batches: an explicit `model_runner.enable_verify_attention`, else
+    `SGLANG_AMD_VERIFY_ATTENTION=0 / 1`, else None = where `kernels.verify_attention_preferred` says it is ahead.  True routes
+    every batch the kernel supports; False keeps the extend kernel.  Decided once per server (baked into captured graphs)."""
+    wanted = getattr(model_runner, "enable_verify_attention", None)
+    if wanted is None:
+        env = os.environ.get("SGLANG_AMD_VERIFY_ATTENTION", "")
+        return None if env not in ("0", "1") else env == "1"
+    return bool(wanted)
+
+
 class HipAttnBackend(AttentionBackend):
     needs_cpu_seq_lens = True
     # qo_indptr / lens are sized per forward, never preallocated at (req pool + 1) (base_attn_backend.py:117-122)
@@ -159,6 +171,9 @@ class HipAttnBackend(AttentionBackend):
         self._seq_i32, self._seq_src, self._seq_i32_in_graph = None, None, False
         self._verify_states, self._verify_nd = {}, 0
         self._verify_mask, self._verify_mask_in_graph = None, False      # the flat tree mask captured verify graphs read (see _verify_mask_buffer)
+        self._verify_ws, self._verify_ws_eager, self._verify_ws_in_graph = None, None, False   # split partials of the verify kernel
+        self.enable_verify_kernel = verify_kernel_wanted(model_runner)
+        self.served = {"verify_attention": 0, "extend_attention": 0}     # forward_extend calls per kernel (tests / telemetry)
         self.debug_flags = 0
         # RadixAttention batches share KV prefixes; the cascade decode path reads a shared prefix once per group (see cascade_wanted)
         self.enable_cascade = cascade_wanted(model_runner) and self.head_dim in (64, 128)
@@ -210,6 +225,12 @@ class HipAttnBackend(AttentionBackend):
             # speculative decoding: the graphs are TARGET_VERIFY forwards of max_num_tokens / max_bs draft tokens per request; their
             # masks hold draft_tokens x (context + draft_tokens) entries per request (triton_backend.py sizes its buffer the same way)
             self._verify_mask = torch.zeros(int(max_num_tokens) * self.max_context_len, dtype=torch.uint8, device=self.device)
+        if max_num_tokens > max_bs:
+            # ... and their split partials: the largest (tokens x splits) any bucket up to max_bs asks for at the context bound
+            nd = max(1, int(max_num_tokens) // max(1, int(max_bs)))
+            need = max(bs * nd * self._verify_splits(bs, nd, self.max_context_len) for bs in range(1, int(max_bs) + 1))
+            if need > 0:
+                self._verify_workspace(need, 1, False)
 
     def get_cuda_graph_seq_len_fill_value(self):
         return 1
@@ -255,6 +276,36 @@ class HipAttnBackend(AttentionBackend):
         self._verify_mask_in_graph |= in_capture
         return buf
 
+    def _verify_splits(self, bs: int, nd: int, max_len: int) -> int:
+        """Splits of the verify kernel for a TARGET_VERIFY batch, 0: the batch stays on the extend kernel."""
+        group = self.num_q_heads // self.num_kv_heads
+        if self.enable_verify_kernel is False or not self.plain_pool or not kernels.verify_attention_supported(nd, group, self.head_dim):
+            return 0
+        if self.enable_verify_kernel is None and not kernels.verify_attention_preferred(bs, self.num_kv_heads, nd, group, max_len):
+            return 0
+        return kernels.choose_verify_splits(bs, self.num_kv_heads, max_len)
+
+    def _verify_workspace(self, tokens: int, splits: int, in_capture: bool):
+        """fp32 partials [tokens, Hq, splits, D] + [tokens, Hq, splits, 2] in ONE flat pair that only grows before graphs exist
+        (the rule of _verify_mask_buffer: referenced by captured graphs -> never reallocated, a larger capture raises, a
+        larger eager batch gets a pair of its own)."""
+        need = tokens * self.num_q_heads * splits
+        ws = self._verify_ws
+        if ws is None or ws[1].numel() < need * 2:
+            if ws is not None and self._verify_ws_in_graph:
+                if in_capture:
+                    raise RuntimeError(f"verify-attention workspace holds {ws[1].numel() // 2} (token, head, split) partials and is referenced by "
+                                       f"captured graphs; capturing {need} needs init_cuda_graph_state(max_bs, max_num_tokens) to cover it")
+                ew = self._verify_ws_eager
+                if ew is None or ew[1].numel() < need * 2:
+                    ew = self._verify_ws_eager = (torch.empty(need * self.head_dim, dtype=torch.float32, device=self.device),
+                                                  torch.empty(need * 2, dtype=torch.float32, device=self.device))
+                return ew
+            ws = self._verify_ws = (torch.empty(need * self.head_dim, dtype=torch.float32, device=self.device),
+                                    torch.empty(need * 2, dtype=torch.float32, device=self.device))
+        self._verify_ws_in_graph |= in_capture
+        return ws
+
     def _verify_state(self, bs: int, nd: int):
         st = self._verify_states.get((bs, nd))
         if st is None:
@@ -297,6 +348,12 @@ class HipAttnBackend(AttentionBackend):
             self._verify_nd = nd
             cm = getattr(fb.spec_info, "custom_mask", None)
             self.forward_metadata.verify_mask = self._verify_mask_buffer(cm, in_capture) if isinstance(cm, torch.Tensor) else None
+            if isinstance(cm, torch.Tensor):
+                # split-KV verify kernel: the split count is fixed here (under capture for any later length), the lengths stay on the device
+                max_len = self.max_context_len if in_capture or fb.seq_lens_cpu is None else int(fb.seq_lens_cpu.max()) + nd
+                splits = self.forward_metadata.verify_splits = self._verify_splits(fb.batch_size, nd, max_len)
+                if splits > 1:
+                    self.forward_metadata.ws_acc, self.forward_metadata.ws_ml = self._verify_workspace(fb.batch_size * nd, splits, in_capture)
         elif fb.forward_mode.is_extend():
             ext = fb.extend_seq_lens_cpu
             qo = torch.zeros(fb.batch_size + 1, dtype=torch.int32)
@@ -385,10 +442,23 @@ class HipAttnBackend(AttentionBackend):
             # the reference's verify call leaves skip_prefix_custom_mask at its default: the prefix is fully visible,
             # the mask decides among the draft tokens only (extend_attention.py:774)
             opt["skip_prefix_custom_mask"] = getattr(forward_batch.forward_mode, "is_target_verify", lambda: False)()
+            # the decode-shaped split-KV kernel where the step's metadata chose it and this LAYER is one it serves (bf16
+            # token-major rows, no window, no cap); everything else keeps the extend kernel
+            if (m.verify_splits > 0 and opt["skip_prefix_custom_mask"] and m.verify_mask is not None
+                    and kernels.verify_attention_supported(m.max_extend_len, layer.tp_q_head_num // layer.tp_k_head_num, layer.qk_head_dim, opt)):
+                kernels.verify_attention(q3, o, self.token_to_kv_pool.get_key_buffer(layer.layer_id),
+                                         self.token_to_kv_pool.get_value_buffer(layer.layer_id),
+                                         self.req_to_token_pool.req_to_token, self._pool_idx(forward_batch), m.seq_lens_i32,
+                                         m.prefix_lens_i32, m.qo_indptr, m.max_extend_len, layer.scaling,
+                                         custom_mask=opt["custom_mask"], mask_indptr=opt["mask_indptr"],
+                                         num_splits=m.verify_splits, ws_acc=m.ws_acc, ws_ml=m.ws_ml)
+                self.served["verify_attention"] += 1
+                return o.view(-1, layer.tp_q_head_num * layer.v_head_dim)
         kernels.extend_attention(q3, o, self.token_to_kv_pool.get_key_buffer(layer.layer_id),
                                  self.token_to_kv_pool.get_value_buffer(layer.layer_id),
                                  self.req_to_token_pool.req_to_token, self._pool_idx(forward_batch), m.seq_lens_i32,
                                  m.prefix_lens_i32, m.qo_indptr, m.max_extend_len, layer.scaling, causal, **opt)
+        self.served["extend_attention"] += 1
         return o.view(-1, layer.tp_q_head_num * layer.v_head_dim)
 
     @staticmethod
