@@ -296,6 +296,40 @@ int sgl_amd_logprobs_from_logits(const void* logits, int logits_is_bf16, int64_t
                                  int ids_is_int64, int64_t batch, int64_t vocab, int n_top, const int32_t* req_offsets,
                                  const int32_t* req_ids, int64_t req_total, float* chosen_logprob, float* top_val, int32_t* top_idx,
                                  float* req_val, int num_splits, void* workspace, void* stream);
+/* The second half of a speculative verify step (speculative_sampling.hip; the reference's build_tree_kernel_efficient,
+ * verify_tree_greedy and tree_speculative_sampling_target_only with zero draft probabilities).  nodes <= sgl_amd_tree_accept_max_nodes()
+ * (64), batch >= 1, batch * nodes <= 65535.
+ *
+ * sgl_amd_build_verify_tree: parents int32 [batch, nodes] (parents[b, 0] = -1, 0 <= parents[b, j] < j), seq_lens int32 [batch] = the
+ * tokens that already have a KV row.  Writes the flat uint8 verify mask (request b's block [nodes, seq_lens[b] + nodes] row-major:
+ * prefix columns 1, tree column c 1 iff node c is the row's node or one of its ancestors; 16-byte aligned buffer of mask_bytes bytes,
+ * nothing is written behind it), mask_indptr int64 [batch + 1], positions int64 [batch * nodes] = seq_lens[b] + depth, next_token
+ * int32 [batch, nodes] (the lowest-index child or -1) and next_sibling (the next higher node with the same parent or -1).
+ *
+ * sgl_amd_tree_accept_from_logits: logits bf16 / fp32 [batch * nodes, vocab], row stride >= vocab (vector loads for 8-byte (bf16) /
+ * 16-byte (fp32) aligned rows, element loads otherwise: same results); temperatures fp32 [batch] or NULL, a request with T <= 0 (or
+ * NULL) is greedy; candidates int32 / int64 [batch, nodes], node 0 = the last sampled token, ids outside [0, vocab) are never read
+ * (probability 0, never the arg-max); uniform fp32 [batch, nodes], uniform_final fp32 [batch] (required with temperatures).
+ * With p = softmax(logits[b, c, :] / T) at the current node c the children are walked in sibling order: prob_acc += p(child token),
+ * the child is accepted if coin <= prob_acc / threshold_acc or p(child token) >= threshold_single (then c = child, prob_acc = 0,
+ * coin = uniform[b, child]; the first coin is uniform[b, 0]), else its token is rejected at c; the walk ends at a node without
+ * children or with every child rejected.  bonus_token = the first column whose inclusive cumulative mass of p with the rejected
+ * tokens at exactly zero exceeds uniform_final[b] * (that total), the last column with residual mass when rounding leaves none.
+ * Greedy requests: a child is accepted iff its token is the arg-max of the node's row (sgl_amd_argmax's order: lowest column on
+ * ties), bonus_token = the arg-max of the last node's row.  Outputs int32: accept_index [batch, nodes] (entry 0 = node 0, then the
+ * accepted nodes in path order, then -1), accept_len [batch] (without node 0), bonus_token [batch], last_node [batch].
+ * num_splits / final_splits: 1..64 column ranges of the pass over all rows / over the batch last rows; workspace: caller-owned,
+ * sgl_amd_tree_accept_workspace_bytes(...) bytes, 8-byte aligned, no initial state.  No [rows, vocab] intermediate is written. */
+int sgl_amd_tree_accept_max_nodes(void);
+int sgl_amd_build_verify_tree(const int32_t* parents, const int32_t* seq_lens, int64_t batch, int nd, void* mask, int64_t mask_bytes,
+                              int64_t* mask_indptr, int64_t* positions, int32_t* next_token, int32_t* next_sibling, void* stream);
+int64_t sgl_amd_tree_accept_workspace_bytes(int64_t batch, int nd, int num_splits, int final_splits);
+int sgl_amd_tree_accept_from_logits(const void* logits, int logits_is_bf16, int64_t row_stride, const float* temperatures,
+                                    const void* candidates, int candidates_is_int64, const int32_t* next_token,
+                                    const int32_t* next_sibling, const float* uniform, const float* uniform_final, float threshold_single,
+                                    float threshold_acc, int64_t batch, int nd, int64_t vocab, int32_t* accept_index, int32_t* accept_len,
+                                    int32_t* bonus_token, int32_t* last_node, int num_splits, int final_splits, void* workspace,
+                                    void* stream);
 /* sgl_kernel.top_k_renorm_prob / top_p_renorm_prob (kernels/aot/python/sgl_kernel/sampling.py:28,79)
  * and sampler.py:753-762 top_p_normalize_probs_torch: zero everything outside the kept sorted
  * prefix and renormalise.  Per-row arrays override the scalar values when non-NULL;

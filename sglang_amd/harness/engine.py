@@ -728,6 +728,74 @@ class Engine:
         r.token_to_kv_pool_allocator.free(slots)
         return logits.view(B, nd, -1)
 
+    def speculative_step(self, tree_tokens: Sequence[Sequence[int]], parents: Sequence, sampling_info: Optional[SamplingBatchInfo] = None,
+                         uniform: Optional[torch.Tensor] = None, uniform_final: Optional[torch.Tensor] = None,
+                         return_logits: bool = False):
+        """One whole speculative step for every running request (eagle_info.py EagleVerifyInput.verify + the commit of
+        eagle_worker.py): the tree tables on the device (kernels.build_verify_tree: no host-built mask), the TARGET_VERIFY forward
+        of verify_tree, tree acceptance + the bonus token straight from its logits (layers/sampler.accept_verified_tree), then the
+        commit: the slots of node 0 and of the accepted nodes move to columns kv .. kv + accept_len of the request's req_to_token row
+        in path order (their rotary positions were kv + depth already), every other draft slot goes back to the allocator, the
+        accepted draft tokens and the bonus token are appended to output_ids -- the request is left as decode_step / finish expect
+        it: the last token has no KV row.  `parents`: one list for every request, or a list per request; tree_tokens[b][0] is the
+        request's last sampled token.  One device-to-host copy (accept_index, accept_len, bonus_token) per step.
+        Returns the per-request lists of appended tokens (and the logits [B, nodes, vocab] on request)."""
+        from ..layers.sampler import accept_verified_tree
+
+        r, dev = self.r, self.device
+        assert r.page_size == 1, "the verify step is wired for page_size 1"
+        self.flush_decode_outputs()
+        self._retire_decode_state()
+        reqs = self.running
+        B = len(reqs)
+        par = [list(p) for p in parents] if isinstance(parents[0], (list, tuple)) else [list(parents)] * B
+        nd = len(par[0])
+        assert len(par) == B and all(len(p) == nd and p[0] == -1 and all(0 <= p[j] < j for j in range(1, nd)) for p in par)
+        assert all(len(t) == nd for t in tree_tokens)
+        assert all(t[0] == q.output_ids[-1] for t, q in zip(tree_tokens, reqs)), "node 0 is the last sampled token"
+        kv = [q.seqlen - 1 for q in reqs]                           # tokens with a KV row
+        slots = self._alloc_token_slots(B * nd)
+        pool_idx = torch.tensor([q.req_pool_idx for q in reqs], dtype=torch.int64, device=dev)
+        kv_dev = torch.tensor(kv, dtype=torch.int32, device=dev)
+        cols = kv_dev.long()[:, None] + torch.arange(nd, device=dev)[None, :]
+        r.req_to_token_pool.req_to_token[pool_idx[:, None], cols] = slots.view(B, nd).to(torch.int32)
+        mask, _, positions, next_token, next_sibling = kernels.build_verify_tree(
+            torch.tensor(par, dtype=torch.int32, device=dev), kv_dev, seq_lens_sum=sum(kv))
+        candidates = torch.tensor([list(t) for t in tree_tokens], dtype=torch.int64, device=dev)
+        fb = ForwardBatch(forward_mode=ForwardMode.TARGET_VERIFY, batch_size=B, input_ids=candidates.view(-1),
+                          req_pool_indices=pool_idx, seq_lens=kv_dev, out_cache_loc=slots, seq_lens_sum=sum(kv),
+                          seq_lens_cpu=torch.tensor(kv, dtype=torch.int64), positions=positions,
+                          req_to_token_pool=r.req_to_token_pool, token_to_kv_pool=r.token_to_kv_pool, attn_backend=r.attn_backend,
+                          spec_info=VerifyInput(custom_mask=mask, draft_token_num=nd, positions=positions))
+        fb.extend_seq_lens_cpu, fb.extend_prefix_lens_cpu, fb.extend_num_tokens = [nd] * B, list(kv), B * nd
+        fb.extend_seq_lens = torch.full((B,), nd, dtype=torch.int32, device=dev)
+        fb.extend_prefix_lens = kv_dev
+        out = r.forward(fb)
+        accept_index, accept_len, bonus, _ = accept_verified_tree(out, sampling_info, candidates, next_token, next_sibling,
+                                                                  uniform, uniform_final)
+        host = torch.cat([accept_index, accept_len[:, None], bonus[:, None]], dim=1).cpu().tolist()
+        # commit: row b keeps the slots of its path at columns kv .. kv + accept_len, the other draft slots are freed
+        keep, keep_rows, keep_cols, appended = [], [], [], []
+        for b, (q, row) in enumerate(zip(reqs, host)):
+            n = row[nd]
+            path = row[:n + 1]
+            keep += [b * nd + c for c in path]
+            keep_rows += [q.req_pool_idx] * (n + 1)
+            keep_cols += list(range(kv[b], kv[b] + n + 1))
+            new = [int(tree_tokens[b][c]) for c in path[1:]] + [row[nd + 1]]
+            q.output_ids.extend(new)
+            appended.append(new)
+        keep_dev = torch.tensor(keep, dtype=torch.int64, device=dev)
+        r.req_to_token_pool.req_to_token[torch.tensor(keep_rows, dtype=torch.int64, device=dev),
+                                         torch.tensor(keep_cols, dtype=torch.int64, device=dev)] = slots[keep_dev].to(torch.int32)
+        dropped = torch.ones(B * nd, dtype=torch.bool, device=dev)
+        dropped[keep_dev] = False
+        if len(keep) < B * nd:
+            r.token_to_kv_pool_allocator.free(slots[dropped])
+        if return_logits:
+            return appended, out.next_token_logits.view(B, nd, -1)
+        return appended
+
     def finish(self, reqs: Sequence[Req]) -> None:
         self.resolve_prefill_ids()
         self.flush_decode_outputs()

@@ -778,6 +778,93 @@ def logprobs_from_logits(logits: torch.Tensor, temperatures: Optional[torch.Tens
     return chosen, top_val, top_idx, req_val
 
 
+# ------------------------------------------------------------- speculative verify: tree tables + acceptance
+def tree_accept_max_nodes() -> int:
+    return native.lib().sgl_amd_tree_accept_max_nodes()
+
+
+def tree_accept_ranges(batch_rows: int, vocab: int) -> int:
+    """Column ranges per row for tree_accept_from_logits: the softmax's count (about 2048 workgroups over the chip, at most 64),
+    never less than 2048 columns a range: one range for short rows."""
+    return max(1, min(64, 2048 // max(1, batch_rows), vocab // 2048))
+
+
+def build_verify_tree(parents: torch.Tensor, seq_lens: torch.Tensor, seq_lens_sum: Optional[int] = None):
+    """The tables of a TARGET_VERIFY step from parent lists, in one launch (speculative_sampling.hip; the reference's
+    build_tree_kernel_efficient).  parents int32 [B, nd] with parents[b, 0] = -1 and 0 <= parents[b, j] < j; seq_lens int32 [B] = tokens
+    that already have a KV row; seq_lens_sum = their sum where the host knows it (None: read back from the device, one synchronise).
+    Returns (custom_mask uint8 flat -- request b's block [nd, seq_lens[b] + nd] row-major, prefix visible, tree part = ancestors incl.
+    the node itself --, mask_indptr int64 [B + 1], positions int64 [B * nd] = seq_lens[b] + depth, next_token int32 [B, nd] = the
+    lowest-index child or -1, next_sibling int32 [B, nd] = the next higher node with the same parent or -1)."""
+    _dev(parents, seq_lens)
+    _need(parents.dim() == 2 and parents.dtype == torch.int32 and parents.is_contiguous(), "build_verify_tree: parents int32 [B, nd] contiguous")
+    B, nd = parents.shape
+    _need(1 <= nd <= tree_accept_max_nodes() and B >= 1 and B * nd <= 65535,
+          f"build_verify_tree: 1 <= nd <= {tree_accept_max_nodes()}, 1 <= B, B * nd <= 65535")
+    _need(seq_lens.dtype == torch.int32 and seq_lens.shape == (B,) and seq_lens.is_contiguous(), "build_verify_tree: seq_lens int32 [B]")
+    dev = parents.device
+    total = int(seq_lens.sum()) if seq_lens_sum is None else int(seq_lens_sum)
+    mask = torch.empty(nd * (total + B * nd), dtype=torch.uint8, device=dev)
+    mask_indptr = torch.empty(B + 1, dtype=torch.int64, device=dev)
+    positions = torch.empty(B * nd, dtype=torch.int64, device=dev)
+    next_token = torch.empty((B, nd), dtype=torch.int32, device=dev)
+    next_sibling = torch.empty((B, nd), dtype=torch.int32, device=dev)
+    native.call("sgl_amd_build_verify_tree", parents.data_ptr(), seq_lens.data_ptr(), B, nd, mask.data_ptr(), mask.numel(),
+                mask_indptr.data_ptr(), positions.data_ptr(), next_token.data_ptr(), next_sibling.data_ptr(), _stream())
+    return mask, mask_indptr, positions, next_token, next_sibling
+
+
+def tree_accept_from_logits(logits: torch.Tensor, temperatures: Optional[torch.Tensor], candidates: torch.Tensor,
+                            next_token: torch.Tensor, next_sibling: torch.Tensor, uniform: Optional[torch.Tensor] = None,
+                            uniform_final: Optional[torch.Tensor] = None, threshold_single: float = 1.0, threshold_acc: float = 1.0):
+    """Which draft tokens of a verified tree are accepted, and the bonus token, straight from the verify forward's logits
+    (speculative_sampling.hip: four launches, the [B * nd, V] logits read once, no probability matrix; the reference's
+    tree_speculative_sampling_target_only with zero draft probabilities, verify_tree_greedy for greedy requests).
+    logits bf16 / fp32 [B * nd, V] (or [B, nd, V]); temperatures fp32 [B] (or [B, 1]) or None: a request with T <= 0, or None, is
+    greedy; candidates int32 / int64 [B, nd] (node 0 = the last sampled token); next_token / next_sibling from build_verify_tree;
+    uniform fp32 [B, nd] and uniform_final fp32 [B]: drawn from torch's device generator when omitted.
+    Returns int32 (accept_index [B, nd]: node 0, the accepted nodes in path order, then -1; accept_len [B]: accepted draft tokens;
+    bonus_token [B]: sampled from the residual distribution at the last accepted node; last_node [B])."""
+    _dev(logits, temperatures, candidates, next_token, next_sibling, uniform, uniform_final)
+    _need(candidates.dim() == 2 and candidates.dtype in (torch.int32, torch.int64) and candidates.is_contiguous(),
+          "tree_accept: candidates int32 / int64 [B, nd] contiguous")
+    B, nd = candidates.shape
+    _need(1 <= nd <= tree_accept_max_nodes() and B >= 1 and B * nd <= 65535,
+          f"tree_accept: 1 <= nd <= {tree_accept_max_nodes()}, 1 <= B, B * nd <= 65535")
+    if logits.dim() == 3 and logits.is_contiguous():
+        logits = logits.view(B * nd, -1)
+    _need(logits.dim() == 2 and logits.stride(1) == 1 and logits.dtype in (torch.float32, _BF16) and logits.shape[0] == B * nd,
+          "tree_accept: fp32 or bf16 [B * nd, V] row-major logits")
+    V = logits.shape[1]
+    _need(1 <= V < 2 ** 31, "tree_accept: 1 <= V < 2^31")
+    for name, tb in (("next_token", next_token), ("next_sibling", next_sibling)):
+        _need(tb.dtype == torch.int32 and tb.shape == (B, nd) and tb.is_contiguous(), f"tree_accept: {name} int32 [B, nd] contiguous")
+    _need(threshold_single > 0 and threshold_acc > 0, "tree_accept: thresholds must be positive")
+    dev = logits.device
+    t = None
+    if temperatures is not None:
+        t = temperatures.reshape(-1)
+        _need(t.dtype == torch.float32 and t.numel() == B and t.is_contiguous(), "tree_accept: temperatures [B] fp32")
+        if uniform is None:
+            uniform = torch.rand((B, nd), dtype=torch.float32, device=dev)
+        if uniform_final is None:
+            uniform_final = torch.rand(B, dtype=torch.float32, device=dev)
+        _need(uniform.dtype == torch.float32 and uniform.shape == (B, nd) and uniform.is_contiguous(), "tree_accept: uniform fp32 [B, nd]")
+        _need(uniform_final.dtype == torch.float32 and uniform_final.shape == (B,) and uniform_final.is_contiguous(),
+              "tree_accept: uniform_final fp32 [B]")
+    accept_index = torch.empty((B, nd), dtype=torch.int32, device=dev)
+    accept_len, bonus_token, last_node = (torch.empty(B, dtype=torch.int32, device=dev) for _ in range(3))
+    splits, final_splits = tree_accept_ranges(B * nd, V), tree_accept_ranges(B, V)
+    # (allocated per call: under graph capture it comes from the graph's pool like every other intermediate)
+    ws = torch.empty(native.lib().sgl_amd_tree_accept_workspace_bytes(B, nd, splits, final_splits) // 8, dtype=torch.int64, device=dev)
+    native.call("sgl_amd_tree_accept_from_logits", logits.data_ptr(), 1 if logits.dtype == _BF16 else 0, logits.stride(0), _ptr(t),
+                candidates.data_ptr(), 1 if candidates.dtype == torch.int64 else 0, next_token.data_ptr(), next_sibling.data_ptr(),
+                _ptr(uniform) if t is not None else None, _ptr(uniform_final) if t is not None else None, float(threshold_single),
+                float(threshold_acc), B, nd, V, accept_index.data_ptr(), accept_len.data_ptr(), bonus_token.data_ptr(),
+                last_node.data_ptr(), splits, final_splits, ws.data_ptr(), _stream())
+    return accept_index, accept_len, bonus_token, last_node
+
+
 def _renorm(probs: torch.Tensor, top_k, top_p) -> torch.Tensor:
     _dev(probs)
     probs = probs.float()

@@ -184,6 +184,26 @@ class Sampler(nn.Module):
             dist.all_reduce(ids, op=dist.ReduceOp.MIN, group=ps.get_tp_group())
 
 
+def accept_verified_tree(logits_output, sampling_info: Optional[SamplingBatchInfo], candidates: torch.Tensor, next_token: torch.Tensor,
+                         next_sibling: torch.Tensor, uniform: Optional[torch.Tensor] = None, uniform_final: Optional[torch.Tensor] = None,
+                         threshold_single: float = 1.0, threshold_acc: float = 1.0):
+    """The accept step of a TARGET_VERIFY forward (eagle_info.py EagleVerifyInput.verify without the [B * nd, V] softmax):
+    `logits_output` = the forward's LogitsProcessorOutput (or its next_token_logits [B * nd, V]), `sampling_info` the batch's
+    (None or all-greedy: verify_tree_greedy), the tree tables from kernels.build_verify_tree.
+    Returns kernels.tree_accept_from_logits' (accept_index, accept_len, bonus_token, last_node)."""
+    logits = getattr(logits_output, "next_token_logits", logits_output)
+    temperatures = None
+    if sampling_info is not None and not sampling_info.is_all_greedy:
+        asked = [n for n, on in (("top-k", sampling_info.need_top_k_sampling), ("top-p", sampling_info.need_top_p_sampling),
+                                 ("min-p", sampling_info.need_min_p_sampling)) if on]
+        if asked:
+            raise NotImplementedError(f"accept_verified_tree: the fused tree-accept path samples from softmax(logits / T) only; "
+                                      f"this batch asks for {', '.join(asked)} filtering, which it does not apply")
+        temperatures = sampling_info.temperatures
+    return kernels.tree_accept_from_logits(logits, temperatures, candidates, next_token, next_sibling, uniform, uniform_final,
+                                           threshold_single, threshold_acc)
+
+
 _SAMPLER_BACKENDS = {"hip": lambda: Sampler()}
 
 
