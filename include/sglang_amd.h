@@ -330,6 +330,38 @@ int sgl_amd_tree_accept_from_logits(const void* logits, int logits_is_bf16, int6
                                     float threshold_acc, int64_t batch, int nd, int64_t vocab, int32_t* accept_index, int32_t* accept_len,
                                     int32_t* bonus_token, int32_t* last_node, int num_splits, int final_splits, void* workspace,
                                     void* stream);
+/* The draft side of a speculative step without a draft model (ngram_draft.hip; the reference's --speculative-algorithm NGRAM): the
+ * request's last tokens are looked up in its own history and what followed the earlier occurrences becomes the draft tree.
+ *
+ * token_table int32 [rows, table_row_stride], 16-byte aligned, table_row_stride = the table's width: a multiple of 4 in [4, 2^27);
+ * request b's history h is token_table[req_pool_indices[b], 0 .. lens[b]), 1 <= lens[b] <= width (held to that range on the device;
+ * tokens behind lens[b] are never used).  req_pool_indices int64 [batch], lens int32 [batch].
+ *
+ * sgl_amd_ngram_draft_tree, with L = lens[b]: node 0 = h[L - 1].  An end position p in [lo, L - 1), lo = max(0, L - 1 - window) for
+ * window > 0 and 0 otherwise, is a hit of length m = the largest m <= max_ngram with h[p - i] == h[L - 1 - i] for all i < m (the
+ * compare may read in front of lo, never in front of 0); it counts if m >= min_ngram.  The `branches` best hits by (m, p) -- longest
+ * first, then the most recent -- are inserted in that order into a trie rooted at node 0, each with its continuation
+ * h[p + 1 .. min(p + depth, L - 1)]: a token follows an existing child with that token or becomes the next node; when nodes are used up
+ * the continuation ends there.  num_real = the nodes so far; the rest of the nd nodes are pad_token, node j's parent being j - 1.
+ * 1 <= nd <= sgl_amd_tree_accept_max_nodes(), 1 <= min_ngram <= max_ngram <= sgl_amd_ngram_draft_max_ngram() (8), 1 <= branches <= 8,
+ * 1 <= depth <= 63, window >= 0.  Outputs: tree_tokens int64 [batch, nd] (the verify forward's input_ids and the accept step's
+ * candidates), parents int32 [batch, nd] (parents[b, 0] = -1, 0 <= parents[b, j] < j, no two siblings with the same token: what
+ * sgl_amd_build_verify_tree takes), num_real int32 [batch].  num_splits: 1..64 workgroups per request, each scanning whole tiles of
+ * sgl_amd_ngram_draft_tile() (1024) end positions; the result does not depend on it.  workspace: caller-owned,
+ * sgl_amd_ngram_draft_workspace_bytes(batch, num_splits) bytes, 4-byte aligned, no initial state.
+ *
+ * sgl_amd_ngram_commit, after sgl_amd_tree_accept_from_logits: writes candidates[b, accept_index[b, i]] for i = 1 .. accept_len[b],
+ * then bonus_token[b], at columns lens[b], lens[b] + 1, ... of the request's row and adds accept_len[b] + 1 to lens[b]; columns at or
+ * behind the width are not written and lens[b] stops at the width. */
+int sgl_amd_ngram_draft_max_ngram(void);
+int sgl_amd_ngram_draft_tile(void);
+int64_t sgl_amd_ngram_draft_workspace_bytes(int64_t batch, int num_splits);
+int sgl_amd_ngram_draft_tree(const int32_t* token_table, int64_t table_row_stride, const int64_t* req_pool_indices, const int32_t* lens,
+                             int64_t batch, int nd, int max_ngram, int min_ngram, int branches, int depth, int window, int64_t pad_token,
+                             int64_t* tree_tokens, int32_t* parents, int32_t* num_real, int num_splits, void* workspace, void* stream);
+int sgl_amd_ngram_commit(int32_t* token_table, int64_t table_row_stride, const int64_t* req_pool_indices, int32_t* lens,
+                         const void* candidates, int candidates_is_int64, const int32_t* accept_index, const int32_t* accept_len,
+                         const int32_t* bonus_token, int64_t batch, int nd, void* stream);
 /* sgl_kernel.top_k_renorm_prob / top_p_renorm_prob (kernels/aot/python/sgl_kernel/sampling.py:28,79)
  * and sampler.py:753-762 top_p_normalize_probs_torch: zero everything outside the kept sorted
  * prefix and renormalise.  Per-row arrays override the scalar values when non-NULL;

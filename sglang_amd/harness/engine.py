@@ -740,8 +740,6 @@ class Engine:
         it: the last token has no KV row.  `parents`: one list for every request, or a list per request; tree_tokens[b][0] is the
         request's last sampled token.  One device-to-host copy (accept_index, accept_len, bonus_token) per step.
         Returns the per-request lists of appended tokens (and the logits [B, nodes, vocab] on request)."""
-        from ..layers.sampler import accept_verified_tree
-
         r, dev = self.r, self.device
         assert r.page_size == 1, "the verify step is wired for page_size 1"
         self.flush_decode_outputs()
@@ -753,15 +751,29 @@ class Engine:
         assert len(par) == B and all(len(p) == nd and p[0] == -1 and all(0 <= p[j] < j for j in range(1, nd)) for p in par)
         assert all(len(t) == nd for t in tree_tokens)
         assert all(t[0] == q.output_ids[-1] for t, q in zip(tree_tokens, reqs)), "node 0 is the last sampled token"
+        pool_idx = torch.tensor([q.req_pool_idx for q in reqs], dtype=torch.int64, device=dev)
+        candidates = torch.tensor([list(t) for t in tree_tokens], dtype=torch.int64, device=dev)
+        appended, logits, _ = self._verify_and_commit(reqs, pool_idx, candidates, torch.tensor(par, dtype=torch.int32, device=dev),
+                                                      sampling_info, uniform, uniform_final, host_tokens=tree_tokens)
+        if return_logits:
+            return appended, logits
+        return appended
+
+    def _verify_and_commit(self, reqs: Sequence[Req], pool_idx: torch.Tensor, candidates: torch.Tensor, parents: torch.Tensor,
+                           sampling_info, uniform, uniform_final, host_tokens=None):
+        """speculative_step behind "the tree is on the device": candidates int64 [B, nd] and parents int32 [B, nd] on the device.
+        `host_tokens`: the candidates as host lists where the caller has them; None = they ride in the step's one device-to-host
+        copy.  Returns (appended tokens per request, logits [B, nd, V], (accept_index, accept_len, bonus_token) on the device)."""
+        from ..layers.sampler import accept_verified_tree
+
+        r, dev = self.r, self.device
+        B, nd = candidates.shape
         kv = [q.seqlen - 1 for q in reqs]                           # tokens with a KV row
         slots = self._alloc_token_slots(B * nd)
-        pool_idx = torch.tensor([q.req_pool_idx for q in reqs], dtype=torch.int64, device=dev)
         kv_dev = torch.tensor(kv, dtype=torch.int32, device=dev)
         cols = kv_dev.long()[:, None] + torch.arange(nd, device=dev)[None, :]
         r.req_to_token_pool.req_to_token[pool_idx[:, None], cols] = slots.view(B, nd).to(torch.int32)
-        mask, _, positions, next_token, next_sibling = kernels.build_verify_tree(
-            torch.tensor(par, dtype=torch.int32, device=dev), kv_dev, seq_lens_sum=sum(kv))
-        candidates = torch.tensor([list(t) for t in tree_tokens], dtype=torch.int64, device=dev)
+        mask, _, positions, next_token, next_sibling = kernels.build_verify_tree(parents, kv_dev, seq_lens_sum=sum(kv))
         fb = ForwardBatch(forward_mode=ForwardMode.TARGET_VERIFY, batch_size=B, input_ids=candidates.view(-1),
                           req_pool_indices=pool_idx, seq_lens=kv_dev, out_cache_loc=slots, seq_lens_sum=sum(kv),
                           seq_lens_cpu=torch.tensor(kv, dtype=torch.int64), positions=positions,
@@ -773,16 +785,20 @@ class Engine:
         out = r.forward(fb)
         accept_index, accept_len, bonus, _ = accept_verified_tree(out, sampling_info, candidates, next_token, next_sibling,
                                                                   uniform, uniform_final)
-        host = torch.cat([accept_index, accept_len[:, None], bonus[:, None]], dim=1).cpu().tolist()
+        parts = [accept_index, accept_len[:, None], bonus[:, None]]
+        if host_tokens is None:
+            parts = [p.long() for p in parts] + [candidates]
+        host = torch.cat(parts, dim=1).cpu().tolist()
         # commit: row b keeps the slots of its path at columns kv .. kv + accept_len, the other draft slots are freed
         keep, keep_rows, keep_cols, appended = [], [], [], []
         for b, (q, row) in enumerate(zip(reqs, host)):
             n = row[nd]
             path = row[:n + 1]
+            toks = host_tokens[b] if host_tokens is not None else row[nd + 2:]
             keep += [b * nd + c for c in path]
             keep_rows += [q.req_pool_idx] * (n + 1)
             keep_cols += list(range(kv[b], kv[b] + n + 1))
-            new = [int(tree_tokens[b][c]) for c in path[1:]] + [row[nd + 1]]
+            new = [int(toks[c]) for c in path[1:]] + [row[nd + 1]]
             q.output_ids.extend(new)
             appended.append(new)
         keep_dev = torch.tensor(keep, dtype=torch.int64, device=dev)
@@ -792,9 +808,82 @@ class Engine:
         dropped[keep_dev] = False
         if len(keep) < B * nd:
             r.token_to_kv_pool_allocator.free(slots[dropped])
+        return appended, out.next_token_logits.view(B, nd, -1), (accept_index, accept_len, bonus)
+
+    # ---- n-gram drafting (the reference's --speculative-algorithm NGRAM): the token history lives on the device --------------
+    _ngram = None
+
+    def _ngram_history(self, reqs: Sequence[Req]):
+        """The device-side token history of the running batch: (table int32 [request-pool rows, context length rounded up to 4],
+        pool_idx int64 [B], lens int32 [B]).  A row is (re)filled from the host's get_fill_ids() whenever the length the device holds
+        for it is not the request's (a new request, plain decode steps in between); otherwise kernels.ngram_commit kept it current."""
+        import numpy as np
+
+        r, dev = self.r, self.device
+        st = self._ngram
+        if st is None:
+            rows, ctx = r.req_to_token_pool.req_to_token.shape
+            st = self._ngram = dict(table=torch.zeros((rows, (ctx + 3) // 4 * 4), dtype=torch.int32, device=dev), owner={}, batch=None)
+        held = [st["owner"].get(q.req_pool_idx, (None, -1)) for q in reqs]
+        stale = [q for q, (who, n) in zip(reqs, held) if who is not q or n != q.seqlen]
+        for q in stale:
+            ids = torch.from_numpy(np.frombuffer(q.get_fill_ids(), dtype=np.int64).astype(np.int32))
+            st["table"][q.req_pool_idx, :ids.numel()].copy_(ids.to(dev, non_blocking=True))
+            st["owner"][q.req_pool_idx] = (q, q.seqlen)
+        key = tuple(q.req_pool_idx for q in reqs)
+        if stale or st["batch"] is None or st["batch"][0] != key:
+            st["batch"] = (key, torch.tensor(key, dtype=torch.int64, device=dev),
+                           torch.tensor([q.seqlen for q in reqs], dtype=torch.int32, device=dev))
+        return st["table"], st["batch"][1], st["batch"][2]
+
+    def ngram_speculative_step(self, nodes: int, max_ngram: int = 4, min_ngram: int = 1, branches: int = 4, window: int = 0,
+                               sampling_info: Optional[SamplingBatchInfo] = None, uniform: Optional[torch.Tensor] = None,
+                               uniform_final: Optional[torch.Tensor] = None, return_logits: bool = False, depth: Optional[int] = None):
+        """speculative_step with the draft made on the device: kernels.ngram_draft_tree proposes a tree of `nodes` nodes per running
+        request from the request's own history (two launches over the device-side token table), the shared verify / accept / commit
+        of speculative_step follows, and kernels.ngram_commit appends what was accepted to the table: draft, tables, forward,
+        acceptance and history update are launches on one stream, with the step's one device-to-host copy (now carrying the drafted
+        tokens too) as the only hand-off.  `depth` (None: nodes - 1) bounds one continuation: below nodes - 1 it leaves nodes for the
+        other branches.  Returns speculative_step's result; with `return_logits` also the drafted
+        (tree_tokens [B, nodes], parents [B, nodes], num_real [B])."""
+        r = self.r
+        assert r.page_size == 1, "the verify step is wired for page_size 1"
+        self.flush_decode_outputs()
+        self._retire_decode_state()
+        reqs = self.running
+        table, pool_idx, lens = self._ngram_history(reqs)
+        assert max(q.seqlen for q in reqs) - 1 + nodes <= r.req_to_token_pool.req_to_token.shape[1], "the draft tree would pass the context length"
+        tree_tokens, parents, num_real = kernels.ngram_draft_tree(table, pool_idx, lens, nodes, max_ngram=max_ngram, min_ngram=min_ngram,
+                                                                  branches=branches, depth=depth, window=window)
+        appended, logits, (accept_index, accept_len, bonus) = self._verify_and_commit(reqs, pool_idx, tree_tokens, parents, sampling_info,
+                                                                                      uniform, uniform_final)
+        kernels.ngram_commit(table, pool_idx, lens, tree_tokens, accept_index, accept_len, bonus)
+        for q in reqs:
+            self._ngram["owner"][q.req_pool_idx] = (q, q.seqlen)
         if return_logits:
-            return appended, out.next_token_logits.view(B, nd, -1)
+            return appended, logits, (tree_tokens, parents, num_real)
         return appended
+
+    def generate_speculative(self, reqs: Sequence[Req], nodes: int, sampling_info: Optional[SamplingBatchInfo] = None, **draft_options) -> None:
+        """Run `reqs` to completion with n-gram speculative steps: prefill, then ngram_speculative_step(nodes, **draft_options) until
+        every request has its max_new_tokens.  A step may overshoot a request's limit: the surplus tokens are dropped and their KV
+        slots freed, so that finish() finds the request as a plain decode would have left it.  Greedy, or sampled through
+        `sampling_info` (one row per request of `reqs`), like generate."""
+        row_of = {id(q): i for i, q in enumerate(reqs)}
+        alloc, req_to_token = self.r.token_to_kv_pool_allocator, self.r.req_to_token_pool.req_to_token
+        self.prefill(reqs, sampling_info)
+        while self.running:
+            done = [q for q in self.running if q.finished()]
+            for q in done:
+                extra = len(q.output_ids) - q.max_new_tokens
+                if extra > 0:                               # rows seqlen - 1 - extra .. seqlen - 2 hold the dropped tokens' KV
+                    alloc.free(req_to_token[q.req_pool_idx, q.seqlen - 1 - extra:q.seqlen - 1].to(torch.int64))
+                    del q.output_ids[q.max_new_tokens:]
+            if done:
+                self.finish(done)
+                continue
+            info = sampling_info.filter_batch([row_of[id(q)] for q in self.running]) if sampling_info is not None else None
+            self.ngram_speculative_step(nodes, sampling_info=info, **draft_options)
 
     def finish(self, reqs: Sequence[Req]) -> None:
         self.resolve_prefill_ids()

@@ -865,6 +865,94 @@ def tree_accept_from_logits(logits: torch.Tensor, temperatures: Optional[torch.T
     return accept_index, accept_len, bonus_token, last_node
 
 
+# ------------------------------------------------------------- speculative draft: n-gram lookup in the request's own history
+NGRAM_MAX_SPLITS = 64
+NGRAM_MAX_BRANCHES = 8
+
+
+def ngram_draft_max_ngram() -> int:
+    return native.lib().sgl_amd_ngram_draft_max_ngram()
+
+
+def ngram_draft_tile() -> int:
+    """End positions a scan workgroup takes through LDS at a time (1024): the unit the splits are made of."""
+    return native.lib().sgl_amd_ngram_draft_tile()
+
+
+def choose_ngram_splits(batch: int, width: int) -> int:
+    """Static split count of the n-gram scan: about two workgroups per CU, every split at least one tile of the table's width, at
+    most NGRAM_MAX_SPLITS."""
+    batch = max(1, batch)
+    want = (2 * _NUM_CUS + batch - 1) // batch
+    return max(1, min(want, width // ngram_draft_tile(), NGRAM_MAX_SPLITS))
+
+
+def _ngram_table_args(who: str, token_table: torch.Tensor, req_pool_indices: torch.Tensor, lens: torch.Tensor) -> Tuple[int, int]:
+    _dev(token_table, req_pool_indices, lens)
+    _need(token_table.dim() == 2 and token_table.dtype == torch.int32 and token_table.is_contiguous(),
+          f"{who}: token_table int32 [rows, width] contiguous")
+    width = token_table.shape[1]
+    _need(width % 4 == 0 and 4 <= width < 2 ** 27, f"{who}: the table's width must be a multiple of 4 in [4, 2^27), got {width}")
+    _need(req_pool_indices.dim() == 1 and req_pool_indices.dtype == torch.int64 and req_pool_indices.is_contiguous(),
+          f"{who}: req_pool_indices int64 [B]")
+    B = req_pool_indices.shape[0]
+    _need(1 <= B <= 65535, f"{who}: 1 <= B <= 65535")
+    _need(lens.dtype == torch.int32 and lens.shape == (B,) and lens.is_contiguous(), f"{who}: lens int32 [B]")
+    return B, width
+
+
+def ngram_draft_tree(token_table: torch.Tensor, req_pool_indices: torch.Tensor, lens: torch.Tensor, nd: int, max_ngram: int = 4,
+                     min_ngram: int = 1, branches: int = 4, depth: Optional[int] = None, window: int = 0, pad_token: int = 0,
+                     num_splits: Optional[int] = None):
+    """A draft tree per request from n-gram lookup in its own history, in two launches (ngram_draft.hip; the reference's
+    --speculative-algorithm NGRAM).  token_table int32 [rows, width]: request b's history (prompt + output) is
+    token_table[req_pool_indices[b], :lens[b]], its last token becomes node 0.  The end positions of the last `window` tokens (0: all)
+    where the history's last min_ngram .. max_ngram tokens occurred before are ranked longest match first, then most recent; the
+    continuations (at most `depth` tokens, None: nd - 1) of the best `branches` are merged into a trie of at most nd nodes, padded to nd
+    with a chain of `pad_token`.  The result does not depend on num_splits (None: choose_ngram_splits).
+    Returns (tree_tokens int64 [B, nd], parents int32 [B, nd] as build_verify_tree takes them, num_real int32 [B])."""
+    B, width = _ngram_table_args("ngram_draft_tree", token_table, req_pool_indices, lens)
+    depth = max(1, nd - 1) if depth is None else depth
+    _need(1 <= nd <= tree_accept_max_nodes(), f"ngram_draft_tree: 1 <= nd <= {tree_accept_max_nodes()}, got {nd}")
+    _need(1 <= min_ngram <= max_ngram <= ngram_draft_max_ngram(),
+          f"ngram_draft_tree: 1 <= min_ngram <= max_ngram <= {ngram_draft_max_ngram()}, got {min_ngram} and {max_ngram}")
+    _need(1 <= branches <= NGRAM_MAX_BRANCHES and 1 <= depth <= tree_accept_max_nodes() - 1 and window >= 0,
+          f"ngram_draft_tree: 1 <= branches <= {NGRAM_MAX_BRANCHES}, 1 <= depth <= {tree_accept_max_nodes() - 1}, window >= 0")
+    splits = choose_ngram_splits(B, width) if num_splits is None else num_splits
+    _need(1 <= splits <= NGRAM_MAX_SPLITS, f"ngram_draft_tree: 1 <= num_splits <= {NGRAM_MAX_SPLITS}, got {splits}")
+    dev = token_table.device
+    tree_tokens = torch.empty((B, nd), dtype=torch.int64, device=dev)
+    parents = torch.empty((B, nd), dtype=torch.int32, device=dev)
+    num_real = torch.empty(B, dtype=torch.int32, device=dev)
+    # (allocated per call: under graph capture it comes from the graph's pool like every other intermediate)
+    ws = torch.empty(native.lib().sgl_amd_ngram_draft_workspace_bytes(B, splits) // 4, dtype=torch.int32, device=dev)
+    native.call("sgl_amd_ngram_draft_tree", token_table.data_ptr(), width, req_pool_indices.data_ptr(), lens.data_ptr(), B, nd, max_ngram,
+                min_ngram, branches, depth, window, int(pad_token), tree_tokens.data_ptr(), parents.data_ptr(), num_real.data_ptr(), splits,
+                ws.data_ptr(), _stream())
+    return tree_tokens, parents, num_real
+
+
+def ngram_commit(token_table: torch.Tensor, req_pool_indices: torch.Tensor, lens: torch.Tensor, candidates: torch.Tensor,
+                 accept_index: torch.Tensor, accept_len: torch.Tensor, bonus_token: torch.Tensor) -> None:
+    """Keep the device-side history current after tree acceptance, in one launch and in place: candidates[b, accept_index[b, i]] for
+    i = 1 .. accept_len[b], then bonus_token[b], go to columns lens[b] ... of the request's row and lens[b] grows by accept_len[b] + 1.
+    Nothing is written at or behind the table's width, where lens stops.  candidates int32 / int64 [B, nd]; accept_index int32 [B, nd],
+    accept_len and bonus_token int32 [B] as tree_accept_from_logits returns them."""
+    B, width = _ngram_table_args("ngram_commit", token_table, req_pool_indices, lens)
+    _dev(candidates, accept_index, accept_len, bonus_token)
+    _need(candidates.dim() == 2 and candidates.shape[0] == B and candidates.dtype in (torch.int32, torch.int64) and candidates.is_contiguous(),
+          "ngram_commit: candidates int32 / int64 [B, nd] contiguous")
+    nd = candidates.shape[1]
+    _need(1 <= nd <= tree_accept_max_nodes(), f"ngram_commit: 1 <= nd <= {tree_accept_max_nodes()}")
+    _need(accept_index.dtype == torch.int32 and accept_index.shape == (B, nd) and accept_index.is_contiguous(),
+          "ngram_commit: accept_index int32 [B, nd] contiguous")
+    for name, t in (("accept_len", accept_len), ("bonus_token", bonus_token)):
+        _need(t.dtype == torch.int32 and t.shape == (B,) and t.is_contiguous(), f"ngram_commit: {name} int32 [B]")
+    native.call("sgl_amd_ngram_commit", token_table.data_ptr(), width, req_pool_indices.data_ptr(), lens.data_ptr(), candidates.data_ptr(),
+                1 if candidates.dtype == torch.int64 else 0, accept_index.data_ptr(), accept_len.data_ptr(), bonus_token.data_ptr(), B, nd,
+                _stream())
+
+
 def _renorm(probs: torch.Tensor, top_k, top_p) -> torch.Tensor:
     _dev(probs)
     probs = probs.float()
