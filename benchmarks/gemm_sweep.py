@@ -117,6 +117,48 @@ def dense_tiled_sweep(args):
         Path(args.json).write_text(json.dumps(rows, indent=1))
 
 
+def fp8_sweep(args):
+    """bf16 vs fp8 (e4m3, per-channel scale) weight-streaming GEMM in ONE run, each with its automatic decomposition: the decode
+    projections of Llama-3-8B and the gate_up of Llama-3-70B at 16 / 64 / 128 rows.  Weights rotate over copies larger than the
+    256 MiB infinity cache; a time is the median of five graph replays of 24 calls."""
+    shapes = [("8b", "qkv", 6144, 4096, "none"), ("8b", "o", 4096, 4096, "none"), ("8b", "gate_up", 28672, 4096, "silu_and_mul"),
+              ("8b", "down", 4096, 14336, "none"), ("70b", "gate_up", 57344, 8192, "silu_and_mul")]
+    rows = []
+    for model, name, N, Kd, ep in shapes:
+        copies = max(2, int(600e6 // (N * Kd)) + 1)
+        w16 = [(torch.randn((N, Kd), device=DEV) * 0.02).to(BF) for _ in range(max(2, copies // 2 + 1))]
+        q = [K.quantize_fp8_weight(w16[i % len(w16)]) for i in range(copies)]
+        for M in (16, 64, 128):
+            x = torch.randn((M, Kd), device=DEV).to(BF)
+            it = [0]
+
+            def run16():
+                it[0] += 1
+                return K.wstream_gemm(x, w16[it[0] % len(w16)], epilogue=ep)
+
+            def run8():
+                it[0] += 1
+                w8, sc = q[it[0] % copies]
+                return K.wstream_gemm(x, w8, epilogue=ep, w_scale=sc)
+
+            row = dict(model=model, shape=name, N=N, K=Kd, M=M, epilogue=ep)
+            for key, fn in (("bf16", run16), ("fp8", run8)):
+                ts = sorted(timeit(fn, reps=1) for _ in range(5))
+                row[key + "_us"] = ts[2] * 1e6
+                row[key + "_spread_us"] = (ts[-1] - ts[0]) * 1e6
+            row["bf16_over_fp8"] = row["bf16_us"] / row["fp8_us"]
+            row["fp8_fraction_of_8TBps"] = N * Kd / (row["fp8_us"] * 1e-6) / HBM_PEAK
+            row["bf16_fraction_of_8TBps"] = N * Kd * 2 / (row["bf16_us"] * 1e-6) / HBM_PEAK
+            row["fp8_decomposition"] = K.choose_wstream_decomposition(M, N, Kd, ep != "none", ep == "silu_and_mul", 1)
+            rows.append(row)
+            print(json.dumps(row), flush=True)
+        del w16, q
+        torch.cuda.empty_cache()
+    if args.json:
+        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.json).write_text(json.dumps(rows, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
@@ -124,9 +166,12 @@ def main():
     ap.add_argument("--M", type=int, default=64)
     ap.add_argument("--blocked", action="store_true", help="chunk-major [K/128, M, 128] activations")
     ap.add_argument("--dense-tiled", action="store_true", help="dense_tiled_gemm vs the library path at M = 256 / 512")
+    ap.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8_e4m3"), help="fp8_e4m3: bf16 vs fp8 weight stream, one run")
     args = ap.parse_args()
     if args.dense_tiled:
         return dense_tiled_sweep(args)
+    if args.weight_dtype == "fp8_e4m3":
+        return fp8_sweep(args)
     shapes = [("gate_up", 28672, 4096), ("down", 4096, 14336), ("qkv", 6144, 4096), ("o", 4096, 4096),
               ("lm_head", 128256, 4096)]
     M = args.M

@@ -444,6 +444,32 @@ int sgl_amd_wstream_moe_gemm(const void* a, const void* w, void* c, const int32_
                              int out_f32, int waves_per_group, void* stream);
 int sgl_amd_wstream_gemm_max_rows(void);
 int64_t sgl_amd_wstream_gemm_workspace_floats(int64_t M, int64_t N, int num_k_splits);
+/* sgl_amd_wstream_gemm over fp8 (OCP e4m3) weights with fp32 scales, weight-only ("W8A16"): x stays bf16, every weight is
+ * widened exactly to bf16 in registers, fp32 accumulate, and the scale is applied to the fp32 accumulator before a split-K
+ * partial is written and before any epilogue:  y = bf16((x . f(w8)^T) * s + bias), epilogues and decompositions as above
+ * (the workspace is sgl_amd_wstream_gemm_workspace_floats; the one-pass silu form needs tiles_per_wave != 1).
+ * Replaces, for decode batches, srt/layers/quantization/fp8.py Fp8LinearMethod.apply (fp8_utils.py apply_fp8_linear: per-token
+ * activation quantisation + a scaled fp8 matmul) -- NOT the same arithmetic: the activations are not quantised here.
+ * w is [N, K] e4m3, w_row_stride in BYTES (a multiple of 16).  scale_mode 0: w_scale[0] for the whole tensor; 1: w_scale[N] per
+ * output channel; 2: w_scale[ceil(N/128)][K/128] per 128 x 128 block, rows scale_row_stride floats apart. */
+int sgl_amd_wstream_gemm_fp8(const void* x, const void* w, const void* bias, void* y, int64_t M, int64_t N,
+                             int64_t K, int64_t x_row_stride, int64_t x_chunk_stride, int64_t w_row_stride,
+                             int64_t y_row_stride, int64_t y_chunk_stride, int epilogue, void* residual,
+                             int64_t residual_row_stride, const void* norm_weight, float eps, int waves_per_group,
+                             int tiles_per_wave, int num_k_splits, void* ws_partials, void* stream,
+                             const float* w_scale, int scale_mode, int64_t scale_row_stride);
+/* sgl_amd_wstream_qkv_rope over an fp8 (e4m3) w_qkv with fp32 scales (contract of sgl_amd_wstream_gemm_fp8): the fp8 GEMM writes
+ * scaled fp32 partials, then the same rope + KV-store combine runs.  Replaces Fp8LinearMethod.apply on QKVParallelLinear ->
+ * RotaryEmbedding.forward_native -> set_kv_buffer (fp8.py, rotary_embedding/utils.py:49-57, base.py:385-417). */
+int sgl_amd_wstream_qkv_rope_fp8(const void* x, const void* w_qkv, const void* bias, void* q_out, int64_t M,
+                                 int64_t K, int num_q_heads, int num_kv_heads, int head_dim,
+                                 int64_t x_row_stride, int64_t x_chunk_stride, int64_t w_row_stride, int64_t q_row_stride,
+                                 const int64_t* positions, const void* cos_sin_cache, int cache_is_f32,
+                                 int64_t rotary_dim, void* k_cache, void* v_cache, const int64_t* cache_loc,
+                                 int64_t cache_row_stride, int kv_fp8, float k_scale, float v_scale,
+                                 int page_size, int kv_layout_hnd, int waves_per_group, int tiles_per_wave,
+                                 int num_k_splits, void* ws_partials, void* stream, const float* w_scale,
+                                 int scale_mode, int64_t scale_row_stride);
 /* Grouped GEMM over moe_align_block_size output: for every row block b < num_tokens_post_padded/block_m
  * with expert e = expert_ids[b]:  c[id, :] = a[id / top_k_div, :] . w[e]^T  for id in
  * sorted_token_ids[b*block_m : (b+1)*block_m] with id < num_valid_ids, optionally scaled by

@@ -738,6 +738,47 @@ void sgl_amd::launch_wstream_combine(const float* part, const uint16_t* bias, ui
   }
 }
 
+int sgl_amd::wstream_combine_norm_max_n() { return kNormThreads * kNormMaxVec * 4; }
+
+void sgl_amd::launch_wstream_combine_norm(const float* part, const uint16_t* bias, uint16_t* y, uint16_t* residual, const uint16_t* norm_w,
+                                          int64_t y_row_stride, int64_t y_chunk_stride, int64_t residual_row_stride, int M, int N,
+                                          int splits, float eps, hipStream_t stream) {
+  CombineParams c{};
+  c.part = part; c.bias = bias; c.y = y; c.residual = residual; c.norm_w = norm_w;
+  c.y_stride = y_row_stride; c.y_cstride = y_chunk_stride; c.res_stride = residual_row_stride;
+  c.M = M; c.N = N; c.splits = splits; c.eps = eps;
+  hipLaunchKernelGGL(wstream_combine_norm_kernel, dim3(c.M), dim3(kNormThreads), 0, stream, c);
+}
+
+int sgl_amd::wstream_qkv_rope_combine(const char* who, WstreamMainFn main_fn, void* ctx, const void* bias, void* q_out, int64_t M,
+                                      int num_q_heads, int num_kv_heads, int head_dim, int64_t q_row_stride, const int64_t* positions,
+                                      const void* cos_sin_cache, int cache_is_f32, int64_t rotary_dim, void* k_cache, void* v_cache,
+                                      const int64_t* cache_loc, int64_t cache_row_stride, int kv_fp8, float k_scale, float v_scale,
+                                      int page_size, int kv_layout_hnd, int num_k_splits, void* ws_partials, hipStream_t st) {
+  SGL_CHECK_ARG(num_q_heads > 0 && num_kv_heads > 0 && head_dim % 16 == 0 && rotary_dim == head_dim,
+                "%s: full-head neox rotary only (head_dim %% 16 == 0, rotary_dim == head_dim)", who);
+  SGL_CHECK_ARG(positions && cos_sin_cache && k_cache && v_cache && cache_loc && q_out, "%s: null argument", who);
+  SGL_CHECK_ARG(q_row_stride % 4 == 0 && cache_row_stride % 4 == 0, "%s: q / cache row strides must be multiples of 4 elements", who);
+  const int64_t N = static_cast<int64_t>(num_q_heads + 2 * num_kv_heads) * head_dim;
+  RopeParams r{};
+  r.part = static_cast<const float*>(ws_partials); r.bias = static_cast<const uint16_t*>(bias);
+  r.q_out = static_cast<uint16_t*>(q_out); r.k_cache = static_cast<uint16_t*>(k_cache); r.v_cache = static_cast<uint16_t*>(v_cache);
+  r.positions = positions; r.cache_loc = cache_loc; r.cos_sin = cos_sin_cache;
+  r.q_stride = q_row_stride; r.cache_row_stride = cache_row_stride;
+  r.M = static_cast<int>(M); r.N = static_cast<int>(N); r.splits = num_k_splits;
+  r.num_q_heads = num_q_heads; r.num_kv_heads = num_kv_heads; r.head_dim = head_dim; r.cache_f32 = cache_is_f32;
+  r.generic = (kv_fp8 || kv_layout_hnd) ? 1 : 0;
+  SGL_CHECK_ARG(!kv_fp8 || (k_scale > 0.f && v_scale > 0.f), "%s: fp8 KV needs positive k_scale / v_scale", who);
+  SGL_CHECK_ARG(make_kv_format(&r.fmt, cache_row_stride, num_kv_heads, head_dim, page_size, kv_layout_hnd, kv_fp8),
+                "%s: HND pools need a power-of-two page_size (got %d); row / page strides below 4 GiB", who, page_size);
+  r.inv_k_scale = kv_fp8 ? 1.0f / k_scale : 1.0f; r.inv_v_scale = kv_fp8 ? 1.0f / v_scale : 1.0f;
+  if (int rc = main_fn(ctx, N, st)) return rc;
+  const int items = (num_q_heads + num_kv_heads) * (head_dim / 8) + num_kv_heads * head_dim / 4;
+  hipLaunchKernelGGL(wstream_combine_rope_kernel, dim3(r.M, (items + 255) / 256), dim3(256), 0, st, r);
+  SGL_CHECK_LAUNCH(who);
+  return 0;
+}
+
 static int g_ws_debug_flags = 0;
 
 extern "C" {
@@ -846,12 +887,10 @@ int sgl_amd_wstream_gemm(const void* x, const void* w, const void* bias, void* y
                            y_row_stride, y_chunk_stride ? y_chunk_stride : 128, static_cast<int>(M), static_cast<int>(N),
                            num_k_splits, epilogue == 1, st);
   } else if (combine) {
-    CombineParams c{};
-    c.part = static_cast<const float*>(ws_partials); c.bias = static_cast<const uint16_t*>(bias); c.y = static_cast<uint16_t*>(y);
-    c.residual = static_cast<uint16_t*>(residual); c.norm_w = static_cast<const uint16_t*>(norm_weight);
-    c.y_stride = y_row_stride; c.y_cstride = y_chunk_stride ? y_chunk_stride : 128; c.res_stride = residual_row_stride;
-    c.M = static_cast<int>(M); c.N = static_cast<int>(N); c.splits = num_k_splits; c.eps = eps;
-    hipLaunchKernelGGL(wstream_combine_norm_kernel, dim3(c.M), dim3(kNormThreads), 0, st, c);
+    launch_wstream_combine_norm(static_cast<const float*>(ws_partials), static_cast<const uint16_t*>(bias), static_cast<uint16_t*>(y),
+                                static_cast<uint16_t*>(residual), static_cast<const uint16_t*>(norm_weight), y_row_stride,
+                                y_chunk_stride ? y_chunk_stride : 128, residual_row_stride, static_cast<int>(M), static_cast<int>(N),
+                                num_k_splits, eps, st);
   }
   SGL_CHECK_LAUNCH("wstream_gemm");
   return 0;
@@ -912,31 +951,22 @@ int sgl_amd_wstream_qkv_rope(const void* x, const void* w_qkv, const void* bias,
                              void* ws_partials, void* stream) {
   SGL_CLEAR_STALE_ERROR();
   if (M == 0) return 0;
-  SGL_CHECK_ARG(num_q_heads > 0 && num_kv_heads > 0 && head_dim % 16 == 0 && rotary_dim == head_dim,
-                "wstream_qkv_rope: full-head neox rotary only (head_dim %% 16 == 0, rotary_dim == head_dim)");
-  SGL_CHECK_ARG(positions && cos_sin_cache && k_cache && v_cache && cache_loc && q_out, "wstream_qkv_rope: null argument");
-  SGL_CHECK_ARG(q_row_stride % 4 == 0 && cache_row_stride % 4 == 0, "wstream_qkv_rope: q / cache row strides must be multiples of 4 elements");
-  const int64_t N = static_cast<int64_t>(num_q_heads + 2 * num_kv_heads) * head_dim;
-  hipStream_t st = as_stream(stream);
-  RopeParams r{};
-  r.part = static_cast<const float*>(ws_partials); r.bias = static_cast<const uint16_t*>(bias);
-  r.q_out = static_cast<uint16_t*>(q_out); r.k_cache = static_cast<uint16_t*>(k_cache); r.v_cache = static_cast<uint16_t*>(v_cache);
-  r.positions = positions; r.cache_loc = cache_loc; r.cos_sin = cos_sin_cache;
-  r.q_stride = q_row_stride; r.cache_row_stride = cache_row_stride;
-  r.M = static_cast<int>(M); r.N = static_cast<int>(N); r.splits = num_k_splits;
-  r.num_q_heads = num_q_heads; r.num_kv_heads = num_kv_heads; r.head_dim = head_dim; r.cache_f32 = cache_is_f32;
-  r.generic = (kv_fp8 || kv_layout_hnd) ? 1 : 0;
-  SGL_CHECK_ARG(!kv_fp8 || (k_scale > 0.f && v_scale > 0.f), "wstream_qkv_rope: fp8 KV needs positive k_scale / v_scale");
-  SGL_CHECK_ARG(make_kv_format(&r.fmt, cache_row_stride, num_kv_heads, head_dim, page_size, kv_layout_hnd, kv_fp8),
-                "wstream_qkv_rope: HND pools need a power-of-two page_size (got %d); row / page strides below 4 GiB", page_size);
-  r.inv_k_scale = kv_fp8 ? 1.0f / k_scale : 1.0f; r.inv_v_scale = kv_fp8 ? 1.0f / v_scale : 1.0f;
-  if (int rc = wstream_launch_main("wstream_qkv_rope", x, w_qkv, nullptr, nullptr, M, N, K, x_row_stride, x_chunk_stride, w_row_stride,
-                                   4, 0, false, tiles_per_wave, true, waves_per_group, num_k_splits, ws_partials, st))
-    return rc;
-  const int items = (num_q_heads + num_kv_heads) * (head_dim / 8) + num_kv_heads * head_dim / 4;
-  hipLaunchKernelGGL(wstream_combine_rope_kernel, dim3(r.M, (items + 255) / 256), dim3(256), 0, st, r);
-  SGL_CHECK_LAUNCH("wstream_qkv_rope");
-  return 0;
+  struct Main {
+    const void *x, *w;
+    int64_t M, K, x_rs, x_cs, w_rs;
+    int nw, tpw, splits;
+    void* ws;
+  } ctx{x, w_qkv, M, K, x_row_stride, x_chunk_stride, w_row_stride, waves_per_group, tiles_per_wave, num_k_splits, ws_partials};
+  return wstream_qkv_rope_combine(
+      "wstream_qkv_rope",
+      [](void* c, int64_t N, hipStream_t st) {
+        const Main& m = *static_cast<const Main*>(c);
+        return wstream_launch_main("wstream_qkv_rope", m.x, m.w, nullptr, nullptr, m.M, N, m.K, m.x_rs, m.x_cs, m.w_rs, 4, 0, false, m.tpw,
+                                   true, m.nw, m.splits, m.ws, st);
+      },
+      &ctx, bias, q_out, M, num_q_heads, num_kv_heads, head_dim, q_row_stride, positions, cos_sin_cache, cache_is_f32, rotary_dim,
+      k_cache, v_cache, cache_loc, cache_row_stride, kv_fp8, k_scale, v_scale, page_size, kv_layout_hnd, num_k_splits, ws_partials,
+      as_stream(stream));
 }
 
 }  // extern "C"

@@ -59,10 +59,22 @@ def _plain_linear(lin) -> bool:
     if hasattr(lin, "base_layer") or hasattr(lin, "set_lora") or hasattr(lin, "lora_backend"):
         return False
     w = getattr(lin, "weight", None)
-    if w is None or w.dtype != _BF16 or w.dim() != 2 or w.stride(1) != 1 or not w.is_cuda:
+    if w is None or w.dim() != 2 or w.stride(1) != 1 or not w.is_cuda:
         return False
     qm = getattr(lin, "quant_method", None)
-    return qm is None or type(qm).__name__ == "UnquantizedLinearMethod"
+    if w.dtype == torch.float8_e4m3fn:
+        # weight-only fp8 (wstream_fp8_gemm.hip): this package's harness Linear only -- e4m3 rows + an fp32 per-channel
+        # `weight_scale`, no quant_method.  The reference's Fp8LinearMethod quantises the activations too (another arithmetic)
+        # and keeps its own path.
+        ws = getattr(lin, "weight_scale", None)
+        return qm is None and isinstance(ws, torch.Tensor) and ws.dtype == torch.float32 and tuple(ws.shape) == (w.shape[0],) and ws.is_cuda
+    return w.dtype == _BF16 and (qm is None or type(qm).__name__ == "UnquantizedLinearMethod")
+
+
+def _w_scale(lin):
+    """The fp32 weight scale of a weight-only fp8 projection (_plain_linear), None for a bf16 one."""
+    ws = getattr(lin, "weight_scale", None)
+    return ws.data if ws is not None else None
 
 
 def layer_unfusable_reason(layer, rows: int) -> Optional[str]:
@@ -108,7 +120,7 @@ def layer_unfusable_reason(layer, rows: int) -> Optional[str]:
     for name, l in lins.items():
         if name == "gate_up_proj" and kernels.wstream_supported(rows, *l.weight.shape):
             continue     # at 65..128 rows the WIDE projection is the library's (wstream_preferred): decode_layer's hybrid form
-        if not kernels.wstream_preferred(rows, *l.weight.shape):
+        if not kernels.wstream_preferred(rows, *l.weight.shape, l.weight.element_size()):
             return f"{name} {tuple(l.weight.shape)} at {rows} rows is left to the library GEMM"
     return None
 
@@ -158,29 +170,30 @@ def decode_layer(layer, positions: torch.Tensor, normed: torch.Tensor, forward_b
     q = kernels.wstream_qkv_rope(normed, attn.qkv_proj.weight.data, bias.data if bias is not None else None, positions,
                                  attn.rotary_emb.cos_sin_cache, attn.num_heads, attn.num_kv_heads, attn.head_dim,
                                  pool.get_key_buffer(layer_id), pool.get_value_buffer(layer_id), forward_batch.out_cache_loc,
-                                 **({} if plain else fmt))
+                                 w_scale=_w_scale(attn.qkv_proj), **({} if plain else fmt))
     a = attn.attn(q, None, None, forward_batch, save_kv_cache=False)
     post = layer.post_attention_layernorm
     blocked_act = mlp.gate_up_proj.weight.shape[0] % 256 == 0
     w_gu = mlp.gate_up_proj.weight.data
     # 65..128 rows: the weight stream still wins for qkv / o / down, the wide gate_up is the library's (kernels.wstream_preferred):
     # the layer keeps its fused combines around a library GEMM + silu_and_mul -- 11 launches instead of the operator path's 15
-    stream_gu = kernels.wstream_preferred(a.shape[0], *w_gu.shape)
+    stream_gu = kernels.wstream_preferred(a.shape[0], *w_gu.shape, w_gu.element_size())
 
     def gate_up(x):
         if stream_gu:
-            return kernels.wstream_gemm(x, w_gu, epilogue="silu_and_mul", out_blocked=blocked_act)
+            return kernels.wstream_gemm(x, w_gu, epilogue="silu_and_mul", out_blocked=blocked_act, w_scale=_w_scale(mlp.gate_up_proj))
         return kernels.silu_and_mul(torch.nn.functional.linear(x, w_gu))
 
     if comm is not None:
-        y = kernels.wstream_gemm(a.reshape(a.shape[0], -1), attn.o_proj.weight.data)
+        y = kernels.wstream_gemm(a.reshape(a.shape[0], -1), attn.o_proj.weight.data, w_scale=_w_scale(attn.o_proj))
         x = comm.all_reduce_add_rmsnorm(y, residual, post.weight.data, post.variance_epsilon)
-        y = kernels.wstream_gemm(gate_up(x), mlp.down_proj.weight.data)
+        y = kernels.wstream_gemm(gate_up(x), mlp.down_proj.weight.data, w_scale=_w_scale(mlp.down_proj))
         return comm.all_reduce_add_rmsnorm(y, residual, next_norm.weight.data, next_norm.variance_epsilon)
     x = kernels.wstream_gemm(a, attn.o_proj.weight.data, epilogue="add_rmsnorm", residual=residual, norm_weight=post.weight.data,
-                             eps=post.variance_epsilon, out_blocked=stream_gu)
+                             eps=post.variance_epsilon, out_blocked=stream_gu, w_scale=_w_scale(attn.o_proj))
     return kernels.wstream_gemm(gate_up(x), mlp.down_proj.weight.data, epilogue="add_rmsnorm", residual=residual,
-                                norm_weight=next_norm.weight.data, eps=next_norm.variance_epsilon, out_blocked=True)
+                                norm_weight=next_norm.weight.data, eps=next_norm.variance_epsilon, out_blocked=True,
+                                w_scale=_w_scale(mlp.down_proj))
 
 
 def decode_layer_moe(layer, positions: torch.Tensor, normed: torch.Tensor, forward_batch, residual: torch.Tensor,
@@ -200,15 +213,15 @@ def decode_layer_moe(layer, positions: torch.Tensor, normed: torch.Tensor, forwa
     q = kernels.wstream_qkv_rope(normed, attn.qkv_proj.weight.data, bias.data if bias is not None else None, positions,
                                  attn.rotary_emb.cos_sin_cache, attn.num_heads, attn.num_kv_heads, attn.head_dim,
                                  pool.get_key_buffer(layer_id), pool.get_value_buffer(layer_id), forward_batch.out_cache_loc,
-                                 **({} if plain else fmt))
+                                 w_scale=_w_scale(attn.qkv_proj), **({} if plain else fmt))
     a = attn.attn(q, None, None, forward_batch, save_kv_cache=False)
     post = layer.post_attention_layernorm
     if comm is not None:
-        y = kernels.wstream_gemm(a.reshape(a.shape[0], -1), attn.o_proj.weight.data)
+        y = kernels.wstream_gemm(a.reshape(a.shape[0], -1), attn.o_proj.weight.data, w_scale=_w_scale(attn.o_proj))
         x = comm.all_reduce_add_rmsnorm(y, residual, post.weight.data, post.variance_epsilon)
     else:
         x = kernels.wstream_gemm(a, attn.o_proj.weight.data, epilogue="add_rmsnorm", residual=residual, norm_weight=post.weight.data,
-                                 eps=post.variance_epsilon)
+                                 eps=post.variance_epsilon, w_scale=_w_scale(attn.o_proj))
     r = moe.gate(x)
     router_logits = r[0] if isinstance(r, tuple) else r              # (ReplicatedLinear returns (output, bias))
     h = moe.experts(x, moe.topk(x, router_logits))

@@ -89,7 +89,8 @@ class ModelRunner:
     def __init__(self, config: ModelConfig, *, max_total_tokens: int, max_running_requests: int,
                  max_context_len: int, page_size: int = 1, device=None, init_device=None,
                  use_graph: bool = True, graph_max_bs: Optional[int] = None, disable_radix_cache: bool = False,
-                 strict_graph: bool = False, kv_cache_dtype: str = "auto", use_hnd: bool = False, vision_config=None):
+                 strict_graph: bool = False, kv_cache_dtype: str = "auto", use_hnd: bool = False, vision_config=None,
+                 weight_dtype: str = "auto"):
         self.config = config
         self.device = device if device is not None else torch.device("cuda", torch.cuda.current_device())
         if self.device.type == "cuda":
@@ -99,7 +100,7 @@ class ModelRunner:
         self.tp_rank = ps.get_tensor_model_parallel_rank()
         self.tp_size = ps.get_tensor_model_parallel_world_size()
         self.page_size = page_size
-        self.model = CausalLM(config, self.device, init_device, self.tp_rank, self.tp_size)
+        self.model = CausalLM(config, self.device, init_device, self.tp_rank, self.tp_size, weight_dtype)   # "fp8_e4m3": weight-only fp8 projections
         self.vision = None
         if vision_config is not None:            # LLaVA: CLIP tower + projector in front of the language model
             from .llava import LlavaVision

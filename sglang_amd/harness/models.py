@@ -99,25 +99,48 @@ def synth_weight(name: str, shape, init_device, std: float = 0.02) -> torch.Tens
 
 class Linear(nn.Module):
     """y = x W^T (+ b), W [out, in] bf16.  Decode batches (M <= 64) stream the weights through the
-    gfx950 wstream GEMM; prefill-sized M uses hipBLASLt via torch (a plain library GEMM)."""
+    gfx950 wstream GEMM; prefill-sized M uses hipBLASLt via torch (a plain library GEMM).
+    weight_dtype="fp8_e4m3": W is stored as e4m3 + a per-output-channel fp32 `weight_scale` (kernels.quantize_fp8_weight,
+    weight-only: y = (x W8^T) * scale + b) and decode batches stream it through the fp8 wstream GEMM."""
 
-    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None):
+    def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, weight_dtype: str = "auto"):
         super().__init__()
+        if weight_dtype not in ("auto", "fp8_e4m3"):
+            raise ValueError(f"weight_dtype must be 'auto' or 'fp8_e4m3', got {weight_dtype!r}")
+        scale = None
+        if weight_dtype == "fp8_e4m3":
+            weight, scale = kernels.quantize_fp8_weight(weight)
         self.weight = nn.Parameter(weight, requires_grad=False)
+        self.weight_scale = nn.Parameter(scale, requires_grad=False) if scale is not None else None
         self.bias = nn.Parameter(bias, requires_grad=False) if bias is not None else None
+
+    @property
+    def _scale(self) -> Optional[torch.Tensor]:
+        return self.weight_scale.data if self.weight_scale is not None else None
 
     def streams(self, x: torch.Tensor) -> bool:
         """x: row-major [M, K], or the chunk-major [K/128, M, 128] form the decode GEMMs hand to each other."""
         rows = x.shape[1] if x.dim() == 3 else x.shape[0]
         return (x.is_cuda and x.dim() in (2, 3) and x.stride(-1) == 1
-                and kernels.wstream_preferred(rows, self.weight.shape[0], self.weight.shape[1]))
+                and kernels.wstream_preferred(rows, self.weight.shape[0], self.weight.shape[1], self.weight.element_size()))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
         if self.streams(x):
-            return kernels.wstream_gemm(x, self.weight.data, self.bias.data if self.bias is not None else None)
+            return kernels.wstream_gemm(x, self.weight.data, self.bias.data if self.bias is not None else None, w_scale=self._scale)
+        if self.weight_scale is not None:
+            return self._forward_fp8_rows(x)
         if self.tiles(x):
             return kernels.dense_tiled_gemm(x, self.weight.data, self.bias.data if self.bias is not None else None)
         return F.linear(kernels.unblock(x), self.weight, self.bias)
+
+    def _forward_fp8_rows(self, x: torch.Tensor) -> torch.Tensor:
+        """More rows than the weight stream takes (prefill) over fp8 weights: widen the weight to bf16 (exact), a plain F.linear,
+        the scale and the bias in fp32, one rounding to bf16.  Harness plumbing, not a hot path: a prefill-sized fp8 GEMM is
+        not part of this package yet."""
+        y = F.linear(kernels.unblock(x), self.weight.to(BF)).float() * self.weight_scale
+        if self.bias is not None:
+            y = y + self.bias.float()
+        return y.to(BF)
 
     def tiles(self, x: torch.Tensor, fused_silu: bool = False) -> bool:
         """129..512 row-major rows where the dense MFMA tile GEMM measured ahead of the library."""
@@ -128,7 +151,7 @@ class Linear(nn.Module):
         """RowParallelLinear.forward (linear.py): all_reduce(self(x)); prefill-sized inputs overlap the collective with
         the matmul piecewise (parallel_state.row_parallel_linear)."""
         if (ps.get_tensor_model_parallel_world_size() > 1 and self.bias is None and x.dim() == 2 and x.shape[0] >= ps.PIECEWISE_MIN_ROWS
-                and not self.streams(x)):
+                and self.weight_scale is None and not self.streams(x)):
             return ps.row_parallel_linear(x, self.weight)
         return ps.tensor_model_parallel_all_reduce(self.forward(x))
 
@@ -138,7 +161,7 @@ class Linear(nn.Module):
         width allows, since only the next projection's GEMM reads them."""
         return kernels.wstream_gemm(x, self.weight.data, self.bias.data if self.bias is not None else None,
                                     epilogue="add_rmsnorm", residual=residual, norm_weight=norm.weight.data,
-                                    eps=norm.variance_epsilon, out_blocked=self.weight.shape[0] % 128 == 0)
+                                    eps=norm.variance_epsilon, out_blocked=self.weight.shape[0] % 128 == 0, w_scale=self._scale)
 
 
 def _shard_rows(w: torch.Tensor, rank: int, world: int) -> torch.Tensor:
@@ -152,14 +175,14 @@ def _shard_cols(w: torch.Tensor, rank: int, world: int) -> torch.Tensor:
 
 
 class LlamaMLP(nn.Module):
-    def __init__(self, cfg: ModelConfig, prefix: str, init_device, device, tp_rank: int, tp_size: int):
+    def __init__(self, cfg: ModelConfig, prefix: str, init_device, device, tp_rank: int, tp_size: int, weight_dtype: str = "auto"):
         super().__init__()
         H, I = cfg.hidden_size, cfg.intermediate_size
         gate = _shard_rows(synth_weight(f"{prefix}.gate_proj", (I, H), init_device), tp_rank, tp_size)
         up = _shard_rows(synth_weight(f"{prefix}.up_proj", (I, H), init_device), tp_rank, tp_size)
         down = _shard_cols(synth_weight(f"{prefix}.down_proj", (H, I), init_device), tp_rank, tp_size)
-        self.gate_up_proj = Linear(torch.cat([gate, up], 0).to(device))     # MergedColumnParallelLinear
-        self.down_proj = Linear(down.to(device))                            # RowParallelLinear
+        self.gate_up_proj = Linear(torch.cat([gate, up], 0).to(device), weight_dtype=weight_dtype)     # MergedColumnParallelLinear
+        self.down_proj = Linear(down.to(device), weight_dtype=weight_dtype)                            # RowParallelLinear
         self.act_fn = SiluAndMul()
 
     def gate_up_act(self, x: torch.Tensor, out_blocked: bool = False) -> torch.Tensor:
@@ -167,8 +190,10 @@ class LlamaMLP(nn.Module):
         request: the fused decode layer hands it to down_proj's GEMM only)."""
         if not OPERATOR_SURFACE_ONLY and self.gate_up_proj.streams(x) and self.gate_up_proj.bias is None:
             return kernels.wstream_gemm(x, self.gate_up_proj.weight.data, epilogue="silu_and_mul",
-                                        out_blocked=out_blocked and self.gate_up_proj.weight.shape[0] % 256 == 0)
-        if not OPERATOR_SURFACE_ONLY and self.gate_up_proj.bias is None and self.gate_up_proj.tiles(x, fused_silu=True):
+                                        out_blocked=out_blocked and self.gate_up_proj.weight.shape[0] % 256 == 0,
+                                        w_scale=self.gate_up_proj._scale)
+        if (not OPERATOR_SURFACE_ONLY and self.gate_up_proj.bias is None and self.gate_up_proj.weight_scale is None
+                and self.gate_up_proj.tiles(x, fused_silu=True)):
             return kernels.dense_tiled_gemm(x, self.gate_up_proj.weight.data, epilogue="silu_and_mul")
         return self.act_fn(self.gate_up_proj(x))
 
@@ -185,7 +210,8 @@ class LlamaMLP(nn.Module):
 
 
 class LlamaAttention(nn.Module):
-    def __init__(self, cfg: ModelConfig, layer_id: int, prefix: str, init_device, device, tp_rank: int, tp_size: int):
+    def __init__(self, cfg: ModelConfig, layer_id: int, prefix: str, init_device, device, tp_rank: int, tp_size: int,
+                 weight_dtype: str = "auto"):
         super().__init__()
         H, D = cfg.hidden_size, cfg.head_dim
         self.total_q, self.total_kv = cfg.num_attention_heads, cfg.num_key_value_heads
@@ -217,9 +243,9 @@ class LlamaAttention(nn.Module):
             else:
                 bks, bvs = bk[kv_rank * D:(kv_rank + 1) * D], bv[kv_rank * D:(kv_rank + 1) * D]
             bias = torch.cat([bq[tp_rank * self.q_size:(tp_rank + 1) * self.q_size], bks, bvs]).to(device)
-        self.qkv_proj = Linear(torch.cat([q, k, v], 0).to(device), bias)    # QKVParallelLinear
+        self.qkv_proj = Linear(torch.cat([q, k, v], 0).to(device), bias, weight_dtype)    # QKVParallelLinear
         wo = synth_weight(f"{prefix}.o_proj", (H, self.total_q * D), init_device)
-        self.o_proj = Linear(_shard_cols(wo, tp_rank, tp_size).to(device))  # RowParallelLinear
+        self.o_proj = Linear(_shard_cols(wo, tp_rank, tp_size).to(device), weight_dtype=weight_dtype)  # RowParallelLinear
         self.rotary_emb = get_rope(D, D, cfg.max_position_embeddings, cfg.rope_theta, True, cfg.rope_scaling, BF, device)
         self.attn = RadixAttention(self.num_heads, D, D ** -0.5, self.num_kv_heads, layer_id, logit_cap=cfg.logit_cap,
                                    sliding_window_size=cfg.sliding_window if cfg.sliding_window is not None else -1)
@@ -247,7 +273,7 @@ class LlamaAttention(nn.Module):
                                          self.qkv_proj.bias.data if self.qkv_proj.bias is not None else None, positions,
                                          self.rotary_emb.cos_sin_cache, self.num_heads, self.num_kv_heads, self.head_dim,
                                          pool.get_key_buffer(self.layer_id), pool.get_value_buffer(self.layer_id),
-                                         forward_batch.out_cache_loc,
+                                         forward_batch.out_cache_loc, w_scale=self.qkv_proj._scale,
                                          **({} if plain_pool else pool.kernel_format(self.attn)))
             attn_output = self.attn(q, None, None, forward_batch, save_kv_cache=False)
             if fused_norm is not None:
@@ -273,16 +299,18 @@ class LlamaAttention(nn.Module):
 
 
 class LlamaDecoderLayer(nn.Module):
-    def __init__(self, cfg: ModelConfig, layer_id: int, init_device, device, tp_rank: int, tp_size: int):
+    def __init__(self, cfg: ModelConfig, layer_id: int, init_device, device, tp_rank: int, tp_size: int, weight_dtype: str = "auto"):
         super().__init__()
         p = f"model.layers.{layer_id}"
-        self.self_attn = LlamaAttention(cfg, layer_id, f"{p}.self_attn", init_device, device, tp_rank, tp_size)
+        dense = cfg.num_local_experts == 0                 # fp8 checkpoints of sparse-MoE models: out of scope, those layers stay bf16
+        self.self_attn = LlamaAttention(cfg, layer_id, f"{p}.self_attn", init_device, device, tp_rank, tp_size,
+                                        weight_dtype if dense else "auto")
         if cfg.num_local_experts > 0:
             from .moe_block import SparseMoeBlock
 
             self.mlp = SparseMoeBlock(cfg, f"{p}.block_sparse_moe", init_device, device, tp_rank, tp_size)
         else:
-            self.mlp = LlamaMLP(cfg, f"{p}.mlp", init_device, device, tp_rank, tp_size)
+            self.mlp = LlamaMLP(cfg, f"{p}.mlp", init_device, device, tp_rank, tp_size, weight_dtype)
         self.input_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, BF, device)
         self.post_attention_layernorm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, BF, device)
 
@@ -338,9 +366,12 @@ class LlamaDecoderLayer(nn.Module):
 class CausalLM(nn.Module):
     """LlamaForCausalLM / Qwen2ForCausalLM / MixtralForCausalLM on one TP rank."""
 
-    def __init__(self, cfg: ModelConfig, device, init_device=None, tp_rank: int = 0, tp_size: int = 1):
+    def __init__(self, cfg: ModelConfig, device, init_device=None, tp_rank: int = 0, tp_size: int = 1, weight_dtype: str = "auto"):
+        """weight_dtype="fp8_e4m3": the four dense projections of every dense layer are e4m3 + per-channel scales (weight-only fp8);
+        lm_head, embeddings, norms and MoE layers stay bf16, as in real FP8 checkpoints.  "auto": bf16 throughout."""
         super().__init__()
         self.config = cfg
+        self.weight_dtype = weight_dtype
         self.device = device
         self.tp_rank, self.tp_size = tp_rank, tp_size
         init_device = init_device if init_device is not None else device
@@ -350,7 +381,7 @@ class CausalLM(nn.Module):
             synth_weight("model.embed_tokens", (cfg.vocab_size, cfg.hidden_size), init_device).to(device),
             requires_grad=False)
         self.layers = nn.ModuleList(
-            [LlamaDecoderLayer(cfg, i, init_device, device, tp_rank, tp_size) for i in range(cfg.num_hidden_layers)])
+            [LlamaDecoderLayer(cfg, i, init_device, device, tp_rank, tp_size, weight_dtype) for i in range(cfg.num_hidden_layers)])
         self.norm = RMSNorm(cfg.hidden_size, cfg.rms_norm_eps, BF, device)
         if cfg.tie_word_embeddings:
             head = self.embed_tokens.data

@@ -1040,6 +1040,51 @@ def skinny_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] =
 
 # --------------------------------------------------------- weight-streaming decode GEMM
 _WS_EPILOGUES = {"none": 0, "silu_and_mul": 1, "add_rmsnorm": 2}
+_E4M3 = torch.float8_e4m3fn
+_FP8_OTHERS = tuple(getattr(torch, n) for n in ("float8_e5m2", "float8_e4m3fnuz", "float8_e5m2fnuz") if hasattr(torch, n))
+
+
+def quantize_fp8_weight(w: torch.Tensor, block: Optional[int] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(w8, scale) of a [N, K] weight for the weight-only fp8 GEMM: w ~ w8.float() * scale.  Per output channel
+    (scale [N] = amax / 448) or, with block=128, per 128 x 128 block (scale [ceil(N/128), K/128]); all-zero rows / blocks get
+    scale 1.  Plain torch: checkpoint preparation, not a hot path."""
+    _need(w.dim() == 2 and block in (None, 128), "quantize_fp8_weight: a 2-D weight, block None or 128")
+    wf = w.float()
+    N, K = wf.shape
+    if block is None:
+        amax = wf.abs().amax(dim=1)
+        scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+        full = scale[:, None]
+    else:
+        _need(K % block == 0, "quantize_fp8_weight: K must be a multiple of the block")
+        nb = (N + block - 1) // block
+        pad = torch.zeros((nb * block, K), dtype=torch.float32, device=w.device)
+        pad[:N] = wf
+        amax = pad.view(nb, block, K // block, block).abs().amax(dim=(1, 3))
+        scale = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+        full = scale.repeat_interleave(block, 0).repeat_interleave(block, 1)[:N]
+    w8 = (wf / full).clamp(-448.0, 448.0).to(_E4M3)
+    return w8, scale.contiguous()
+
+
+def _fp8_scale_args(who: str, w: torch.Tensor, w_scale: Optional[torch.Tensor], N: int, K: int) -> tuple:
+    """The (w_scale, scale_mode, scale_row_stride) tail of the fp8 entry points; () for bf16 weights."""
+    _need(w.dtype not in _FP8_OTHERS, f"{who}: fp8 weights must be float8_e4m3fn (got {w.dtype})")
+    if w.dtype != _E4M3:
+        _need(w_scale is None, f"{who}: w_scale goes with float8_e4m3fn weights only")
+        return ()
+    _need(w_scale is not None, f"{who}: float8_e4m3fn weights need w_scale")
+    _need(w_scale.dtype == torch.float32 and w_scale.device == w.device, f"{who}: w_scale must be fp32 on the weights' device (got {w_scale.dtype})")
+    _need(w.stride(0) % 16 == 0 and w.data_ptr() % 16 == 0, f"{who}: fp8 weight rows must be 16-byte aligned")
+    shape = tuple(w_scale.shape)
+    if shape in ((), (1,)):
+        return w_scale.data_ptr(), 0, 0
+    if shape == (N,):
+        _need(w_scale.is_contiguous(), f"{who}: per-channel w_scale must be contiguous")
+        return w_scale.data_ptr(), 1, 0
+    _need(K % 128 == 0 and shape == ((N + 127) // 128, K // 128) and w_scale.stride(1) == 1,
+          f"{who}: w_scale is (), (N,) or (ceil(N/128), K/128) fp32 (got {shape} for N={N} K={K})")
+    return w_scale.data_ptr(), 2, w_scale.stride(0)
 
 
 def wstream_gemm_max_rows() -> int:
@@ -1058,20 +1103,24 @@ WSTREAM_SILU_INTERLEAVED = False
 
 
 @functools.lru_cache(maxsize=None)
-def wstream_preferred(M: int, N: int, K: int) -> bool:
+def wstream_preferred(M: int, N: int, K: int, w_bytes: int = 2) -> bool:
     """Policy on top of wstream_supported(): up to 64 rows the weight stream always beats the library GEMM
     on MI355X; at 65..128 rows it still does for the narrow projections (N <= 8192: qkv / o / down), while
-    the wide ones (gate_up, lm_head) are left to hipBLASLt (benchmarks/gemm_sweep.py --M 128)."""
-    return wstream_supported(M, N, K) and (M <= 64 or N <= 8192)
+    the wide ones (gate_up, lm_head) are left to hipBLASLt (benchmarks/gemm_sweep.py --M 128).
+    w_bytes = 1 (e4m3 weights): whatever is supported -- there is no library alternative to weigh against."""
+    return wstream_supported(M, N, K) and (w_bytes == 1 or M <= 64 or N <= 8192)
 
 
 @functools.lru_cache(maxsize=None)
-def choose_wstream_config(M: int, N: int, K: int, need_combine: bool = False, fused_silu: bool = False) -> Tuple[int, int]:
+def choose_wstream_config(M: int, N: int, K: int, need_combine: bool = False, fused_silu: bool = False, w_bytes: int = 2) -> Tuple[int, int]:
     """(waves_per_group, k_splits) for y[M,N] = x . w[N,K]^T.  One workgroup per CU is resident (its
     LDS ring holds the in-flight chunks), so the best grids are whole 256-group rounds.  The cost model
     is fitted to benchmarks/gemm_sweep.py on MI355X: a busy CU streams <= ~24 GB/s, the chip <= ~5.5 TB/s,
-    ~2 us of pipeline fill, and split-K pays the fp32 partial round trip plus the combine launch."""
+    ~2 us of pipeline fill, and split-K pays the fp32 partial round trip plus the combine launch.
+    w_bytes = 1 (e4m3 weights, wstream_fp8_gemm.hip): the same model over half the bytes per workgroup -- the rates are the bf16
+    sweep's: unmeasured guesses for the fp8 kernel, NOT yet re-fitted to its own sweep (profiles/wstream_fp8_gemm_sweep.json)."""
     tiles, nch = N // 16, K // 128
+    tile_bytes = 2048 * w_bytes       # a 16-row tile of one 128-wide K chunk
     best = None
     if fused_silu:                    # one pass, each wave owns a gate tile and its up tile: no split-K
         tiles //= 2
@@ -1080,7 +1129,7 @@ def choose_wstream_config(M: int, N: int, K: int, need_combine: bool = False, fu
         groups = (tiles + nw - 1) // nw
         for s in range(1, 2 if fused_silu else max(1, min(nch // 2, 32)) + 1):
             wgs = groups * s
-            wg_bytes = nw * ((nch + s - 1) // s) * (8192 if fused_silu else 4096)
+            wg_bytes = nw * ((nch + s - 1) // s) * (2 * tile_bytes if fused_silu else tile_bytes)
             full, rem = divmod(wgs, _NUM_CUS)
             t = 2.0e-6 + full * _NUM_CUS * wg_bytes / 5.5e12
             if rem:
@@ -1114,13 +1163,16 @@ def unblock(x: torch.Tensor) -> torch.Tensor:
 
 
 @functools.lru_cache(maxsize=None)
-def choose_wstream_decomposition(M: int, N: int, K: int, need_combine: bool = False, fused_silu: bool = False) -> Tuple[int, int, int]:
+def choose_wstream_decomposition(M: int, N: int, K: int, need_combine: bool = False, fused_silu: bool = False,
+                                 w_bytes: int = 2) -> Tuple[int, int, int]:
     """(waves_per_group, tiles_per_wave, k_splits).  On top of choose_wstream_config(): a launch without split-K
     whose rows fit 64 may give every wave two output tiles (t and t + N/32) -- half the activation traffic per weight
     byte: lm_head 200 -> 174 us, the unfused gate_up 39.6 -> 39.1 (benchmarks/gemm_sweep.py --blocked).  With split-K
-    the two-tile forms measured no faster (down 27.8 vs 27.5 us), so those keep one tile per wave."""
-    nw, s = choose_wstream_config(M, N, K, need_combine, fused_silu)
+    the two-tile forms measured no faster (down 27.8 vs 27.5 us), so those keep one tile per wave.
+    w_bytes = 1 (e4m3 weights): the same choices over half the bytes per tile (rates: see choose_wstream_config)."""
+    nw, s = choose_wstream_config(M, N, K, need_combine, fused_silu, w_bytes)
     nch = K // 128
+    tile_bytes = 2048 * w_bytes
 
     def rounds_time(groups: int, wg_bytes: int, chip: float, per_cu: float) -> float:
         full, rem = divmod(groups, _NUM_CUS)
@@ -1134,20 +1186,20 @@ def choose_wstream_decomposition(M: int, N: int, K: int, need_combine: bool = Fa
         # (nw, 1) = every wave ONE tile of 8 gate + 8 up rows (N / 16 tiles).  The second one exists for the widths whose pairs
         # do not make whole rounds of the chip: Llama-3-8B gate_up has 896 pairs = 224 workgroups of 4 waves (32 CUs idle)
         # but 1792 tiles = 256 workgroups of 7 waves (measured equal: see WSTREAM_SILU_INTERLEAVED)
-        best = (rounds_time((N // 32 + nw - 1) // nw, nw * nch * 8192, 6.0e12, 26e9), nw, 2)
-        if WSTREAM_SILU_INTERLEAVED and M <= 64 and N % 16 == 0:
+        best = (rounds_time((N // 32 + nw - 1) // nw, nw * nch * 2 * tile_bytes, 6.0e12, 26e9), nw, 2)
+        if WSTREAM_SILU_INTERLEAVED and w_bytes == 2 and M <= 64 and N % 16 == 0:
             for nw1 in (8, 7, 6, 5, 4):
-                t1 = rounds_time((N // 16 + nw1 - 1) // nw1, nw1 * nch * 4096, 6.4e12, 26e9)
+                t1 = rounds_time((N // 16 + nw1 - 1) // nw1, nw1 * nch * tile_bytes, 6.4e12, 26e9)
                 if t1 < best[0] * 0.97:
                     best = (t1, nw1, 1)
         return best[1], best[2], s
     if s != 1 or M > 64 or N % 32 != 0:
         return nw, 1, s
 
-    one = rounds_time((N // 16 + nw - 1) // nw, nw * nch * 4096, 5.3e12, 24e9)
+    one = rounds_time((N // 16 + nw - 1) // nw, nw * nch * tile_bytes, 5.3e12, 24e9)
     best = (one, nw, 1)
     for nw2 in (4, 3, 2):
-        two = rounds_time((N // 32 + nw2 - 1) // nw2, nw2 * nch * 8192, 6.0e12, 26e9)
+        two = rounds_time((N // 32 + nw2 - 1) // nw2, nw2 * nch * 2 * tile_bytes, 6.0e12, 26e9)
         if two < best[0] * 0.98:
             best = (two, nw2, 2)
     return best[1], best[2], 1
@@ -1156,15 +1208,22 @@ def choose_wstream_decomposition(M: int, N: int, K: int, need_combine: bool = Fa
 def wstream_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: str = "none",
                  residual: Optional[torch.Tensor] = None, norm_weight: Optional[torch.Tensor] = None, eps: float = 0.0,
                  out: Optional[torch.Tensor] = None, waves_per_group: Optional[int] = None,
-                 splits: Optional[int] = None, out_blocked: bool = False, tiles_per_wave: Optional[int] = None) -> torch.Tensor:
+                 splits: Optional[int] = None, out_blocked: bool = False, tiles_per_wave: Optional[int] = None,
+                 w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decode-batch F.linear(x, w, bias) on the weight-streaming kernel, optionally followed (in the
     split-K combine kernel) by silu_and_mul or by fused_add_rmsnorm(out, residual, norm_weight, eps).
-    x may be chunk-major (see _x_layout); out_blocked=True returns the result chunk-major."""
+    x may be chunk-major (see _x_layout); out_blocked=True returns the result chunk-major.
+    w may be torch.float8_e4m3fn with fp32 `w_scale` of shape () / (1,), (N,) or (ceil(N/128), K/128): weight-only fp8
+    (wstream_fp8_gemm.hip), the linear being (x . w^T) * scale in fp32."""
     _dev(x, w)
-    _need(x.dtype == _BF16 and w.dtype == _BF16 and w.dim() == 2, "wstream_gemm: bf16 x / 2-D bf16 w")
+    _need(x.dtype == _BF16 and w.dtype in (_BF16, _E4M3) and w.dim() == 2,
+          f"wstream_gemm: bf16 x / 2-D bf16 or float8_e4m3fn w (got {w.dtype})")
     M, K, x_rs, x_cs = _x_layout(x, "wstream_gemm")
     N = w.shape[0]
     _need(w.shape[1] == K and w.stride(1) == 1, "wstream_gemm: shapes / contiguity")
+    fp8 = w.dtype == _E4M3
+    w_bytes = 1 if fp8 else 2
+    scale_args = _fp8_scale_args("wstream_gemm", w, w_scale, N, K)
     ep = _WS_EPILOGUES[epilogue]
     n_out = N // 2 if ep == 1 else N
     if out is None:
@@ -1180,9 +1239,9 @@ def wstream_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
         # silu_and_mul: one pass with two tiles per wave when the caller does not force a split
         one_pass = ep == 1 and splits in (None, 1) and (N % 32 == 0 or (tiles_per_wave == 1 and N % 16 == 0)) and bias is None
         if waves_per_group is None and splits is None and tiles_per_wave is None:
-            nw_auto, tpw_auto, s_auto = choose_wstream_decomposition(M, N, K, ep != 0, one_pass)
+            nw_auto, tpw_auto, s_auto = choose_wstream_decomposition(M, N, K, ep != 0, one_pass, w_bytes)
         else:
-            nw_auto, s_auto = choose_wstream_config(M, N, K, ep != 0, one_pass)
+            nw_auto, s_auto = choose_wstream_config(M, N, K, ep != 0, one_pass, w_bytes)
     nw = waves_per_group or nw_auto
     s = splits or s_auto
     one_pass = ep == 1 and s == 1 and (N % 32 == 0 or (tiles_per_wave == 1 and N % 16 == 0)) and bias is None
@@ -1192,9 +1251,9 @@ def wstream_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] 
     # multiple of 16 but not of 32 runs the interleaved one-pass form when the automatic decomposition says one tile per wave
     one_pass = ep == 1 and s == 1 and bias is None and (N % 16 == 0 if tpw == 1 else N % 32 == 0)
     ws = _gemm_workspace(x.device, native.lib().sgl_amd_wstream_gemm_workspace_floats(M, N, s)) if ((s > 1 or ep) and not one_pass) else None
-    native.call("sgl_amd_wstream_gemm", x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, x_rs, x_cs,
-                w.stride(0), y_rs, y_cs, ep, _ptr(residual), residual.stride(0) if residual is not None else 0,
-                _ptr(norm_weight), float(eps), nw, tpw, s, _ptr(ws), _stream())
+    native.call("sgl_amd_wstream_gemm_fp8" if fp8 else "sgl_amd_wstream_gemm", x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(),
+                M, N, K, x_rs, x_cs, w.stride(0), y_rs, y_cs, ep, _ptr(residual), residual.stride(0) if residual is not None else 0,
+                _ptr(norm_weight), float(eps), nw, tpw, s, _ptr(ws), _stream(), *scale_args)
     return out
 
 
@@ -1280,15 +1339,18 @@ def wstream_qkv_rope(x: torch.Tensor, w_qkv: torch.Tensor, bias: Optional[torch.
                      k_cache: torch.Tensor, v_cache: torch.Tensor, cache_loc: torch.Tensor,
                      waves_per_group: Optional[int] = None, splits: Optional[int] = None,
                      tiles_per_wave: Optional[int] = None, kv_fp8: bool = False, k_scale: float = 1.0,
-                     v_scale: float = 1.0, page_size: int = 1, hnd: bool = False) -> torch.Tensor:
+                     v_scale: float = 1.0, page_size: int = 1, hnd: bool = False,
+                     w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """Decode-batch qkv_proj + neox rotary embedding + KV-pool store (one GEMM + combine pair): returns the
     rotated q [M, Hq*D]; the rotated k rows and the v rows land in k_cache / v_cache at cache_loc, in the pool's
-    format (kv_fp8 / hnd as in store_kv_cache)."""
+    format (kv_fp8 / hnd as in store_kv_cache).  w_qkv may be float8_e4m3fn with fp32 `w_scale` (see wstream_gemm)."""
     _dev(x, w_qkv, positions, cos_sin_cache, k_cache, v_cache, cache_loc)
     M, K, x_rs, x_cs = _x_layout(x, "wstream_qkv_rope")
     N = (num_q_heads + 2 * num_kv_heads) * head_dim
-    _need(x.dtype == _BF16 and w_qkv.dtype == _BF16 and w_qkv.shape == (N, K) and w_qkv.stride(1) == 1,
-          "wstream_qkv_rope: x [M,K] / w_qkv [(Hq+2Hkv)*D, K] bf16")
+    _need(x.dtype == _BF16 and w_qkv.dtype in (_BF16, _E4M3) + _FP8_OTHERS and w_qkv.shape == (N, K) and w_qkv.stride(1) == 1,
+          "wstream_qkv_rope: x [M,K] bf16 / w_qkv [(Hq+2Hkv)*D, K] bf16 or float8_e4m3fn")
+    scale_args = _fp8_scale_args("wstream_qkv_rope", w_qkv, w_scale, N, K)
+    fp8 = w_qkv.dtype == _E4M3
     _need(positions.dtype == torch.int64 and cache_loc.dtype == torch.int64 and positions.numel() == M and cache_loc.numel() == M,
           "wstream_qkv_rope: int64 positions / cache_loc of length M")
     _need(cos_sin_cache.dtype in (_BF16, torch.float32) and cos_sin_cache.is_contiguous() and cos_sin_cache.shape[-1] == head_dim,
@@ -1305,15 +1367,15 @@ def wstream_qkv_rope(x: torch.Tensor, w_qkv: torch.Tensor, bias: Optional[torch.
               "wstream_qkv_rope: bf16 KV pool rows of Hkv*D")
         cache_rs = kc.stride(0)
     if waves_per_group is None or splits is None:
-        nw_auto, s_auto = choose_wstream_config(M, N, K, True)
+        nw_auto, s_auto = choose_wstream_config(M, N, K, True, False, 1 if fp8 else 2)
     nw, s = waves_per_group or nw_auto, splits or s_auto
     q_out = torch.empty((M, num_q_heads * head_dim), dtype=_BF16, device=x.device)
     ws = _gemm_workspace(x.device, native.lib().sgl_amd_wstream_gemm_workspace_floats(M, N, s))
-    native.call("sgl_amd_wstream_qkv_rope", x.data_ptr(), w_qkv.data_ptr(), _ptr(bias), q_out.data_ptr(), M, K, num_q_heads,
+    native.call("sgl_amd_wstream_qkv_rope_fp8" if fp8 else "sgl_amd_wstream_qkv_rope", x.data_ptr(), w_qkv.data_ptr(), _ptr(bias), q_out.data_ptr(), M, K, num_q_heads,
                 num_kv_heads, head_dim, x_rs, x_cs, w_qkv.stride(0), q_out.stride(0), positions.data_ptr(),
                 cos_sin_cache.data_ptr(), 1 if cos_sin_cache.dtype == torch.float32 else 0, cos_sin_cache.shape[-1],
                 kc.data_ptr(), vc.data_ptr(), cache_loc.data_ptr(), cache_rs, 1 if kv_fp8 else 0, float(k_scale), float(v_scale),
-                int(page_size), 1 if hnd else 0, nw, tiles_per_wave or 1, s, ws.data_ptr(), _stream())
+                int(page_size), 1 if hnd else 0, nw, tiles_per_wave or 1, s, ws.data_ptr(), _stream(), *scale_args)
     return q_out
 
 
