@@ -159,6 +159,88 @@ def fp8_sweep(args):
         Path(args.json).write_text(json.dumps(rows, indent=1))
 
 
+def fp8_tiled_sweep(args):
+    """The fp8-weight MFMA tile GEMM (dense_tiled_gemm with w_scale, automatic tile / splits) at prefill-sized rows, per shape
+    against (b) the path it replaces -- widen the weight to bf16, F.linear, scale in fp32, round (+ the silu_and_mul kernel for
+    the fused gate_up) -- and (c) the bf16 path on bf16 weights (dense_tiled_gemm where dense_tiled_preferred(), the library GEMM
+    elsewhere).  The three are captured as graphs in one process and replayed alternately, 5 timed repetitions each (device
+    events): median, spread (max - min) and the new kernel's share of the bf16 MFMA roofline max(flops / peak, fp8 bytes / HBM
+    peak).  Rows 96 and 128 are measured too (the policy leaves them on the weight stream)."""
+    rows = []
+    reps = 5
+    for model, name, N, Kd in [s for s in DENSE_TILED_SHAPES if s[1] != "lm_head"]:      # lm_head stays bf16 in an fp8 engine
+        copies = max(2, min(6, int(600e6 // (N * Kd)) + 1))   # rotate so the weights come from HBM, not the infinity cache
+        w16 = [(torch.randn((N, Kd), device=DEV) * 0.02).to(BF) for _ in range(2)]
+        q = [K.quantize_fp8_weight(w16[i % 2]) for i in range(copies)]
+        it = [0]
+
+        def nxt8():
+            it[0] = (it[0] + 1) % copies
+            return q[it[0]]
+
+        def nxt16():
+            it[0] = (it[0] + 1) % copies
+            return w16[it[0] % 2]
+
+        for M in (96, 128, 256, 512, 2048, 8192):
+            x = torch.randn((M, Kd), device=DEV).to(BF)
+            for fused in ((False, True) if name == "gate_up" else (False,)):
+                n_out = N // 2 if fused else N
+                out = torch.empty((M, n_out), dtype=BF, device=DEV)
+                flops = 2 * M * N * Kd
+                t_hbm, t_mfma = (N * Kd + (M * Kd + M * n_out) * 2) / HBM_PEAK, flops / MFMA_PEAK
+                iters = max(2, min(24, int(20e-3 / (flops / 4e14 + 20e-6))))      # a graph of ~20 ms at most
+
+                def new_fn():
+                    w8, sc = nxt8()
+                    K.dense_tiled_gemm(x, w8, epilogue="silu_and_mul" if fused else "none", out=out, w_scale=sc)
+
+                def old_fn():
+                    w8, sc = nxt8()
+                    y = (F.linear(x, w8.to(BF)).float() * sc).to(BF)
+                    if fused:
+                        K.silu_and_mul(y, out=out)
+
+                def bf16_fn():
+                    w = nxt16()
+                    if K.dense_tiled_preferred(M, N, Kd, fused):
+                        K.dense_tiled_gemm(x, w, out=out)
+                    elif fused:
+                        K.silu_and_mul(F.linear(x, w), out=out)
+                    else:
+                        F.linear(x, w)
+
+                graphs = {"fp8_tiled": graph_of(new_fn, iters, 2), "widen_library": graph_of(old_fn, iters, 2), "bf16": graph_of(bf16_fn, iters, 2)}
+                times = {k: [] for k in graphs}
+                for _ in range(reps):
+                    for key, g in graphs.items():
+                        s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                        s.record()
+                        g.replay()
+                        e.record()
+                        torch.cuda.synchronize()
+                        times[key].append(s.elapsed_time(e) / iters * 1e-3)
+                bn, sp = K.choose_dense_tiled_fp8_config(M, N, Kd, fused)
+                row = dict(model=model, shape=name, fused_silu=fused, M=M, N=N, K=Kd, block_n=bn, splits=sp, calls_per_graph=iters,
+                           bound="hbm" if t_hbm >= t_mfma else "mfma", bound_us=max(t_hbm, t_mfma) * 1e6)
+                for key, ts in times.items():
+                    med = sorted(ts)[len(ts) // 2]
+                    row[key] = dict(median_us=med * 1e6, spread_us=(max(ts) - min(ts)) * 1e6)
+                row["fp8_tiled"]["share_of_bound"] = row["bound_us"] / row["fp8_tiled"]["median_us"]
+                row["widen_library_over_fp8_tiled"] = row["widen_library"]["median_us"] / row["fp8_tiled"]["median_us"]
+                row["bf16_over_fp8_tiled"] = row["bf16"]["median_us"] / row["fp8_tiled"]["median_us"]
+                row["fp8_tiled_slower_than_widen_library"] = (row["fp8_tiled"]["median_us"] - row["widen_library"]["median_us"]
+                                                              > max(row["fp8_tiled"]["spread_us"], row["widen_library"]["spread_us"]))
+                rows.append(row)
+                print(json.dumps(row), flush=True)
+                del graphs
+        del w16, q
+        torch.cuda.empty_cache()
+    if args.json:
+        Path(args.json).parent.mkdir(parents=True, exist_ok=True)
+        Path(args.json).write_text(json.dumps(rows, indent=1))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
@@ -166,8 +248,10 @@ def main():
     ap.add_argument("--M", type=int, default=64)
     ap.add_argument("--blocked", action="store_true", help="chunk-major [K/128, M, 128] activations")
     ap.add_argument("--dense-tiled", action="store_true", help="dense_tiled_gemm vs the library path at M = 256 / 512")
-    ap.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8_e4m3"), help="fp8_e4m3: bf16 vs fp8 weight stream, one run")
+    ap.add_argument("--weight-dtype", default="bf16", choices=("bf16", "fp8_e4m3"), help="fp8_e4m3: bf16 vs fp8 weight stream, one run; with --dense-tiled: the fp8-weight tile GEMM at 96..8192 rows")
     args = ap.parse_args()
+    if args.dense_tiled and args.weight_dtype == "fp8_e4m3":
+        return fp8_tiled_sweep(args)
     if args.dense_tiled:
         return dense_tiled_sweep(args)
     if args.weight_dtype == "fp8_e4m3":

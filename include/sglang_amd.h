@@ -692,6 +692,22 @@ int sgl_amd_dense_tiled_gemm_min_rows(void);
 int sgl_amd_dense_tiled_gemm_max_rows(void);
 int64_t sgl_amd_dense_tiled_gemm_workspace_floats(int64_t M, int64_t N, int num_k_splits);
 
+/* ---- dense MFMA tile GEMM over fp8 (e4m3) weights, any row count (reference: srt/layers/quantization/fp8.py
+ *      Fp8LinearMethod.apply for prefill-sized inputs; epilogue 1: + srt/layers/activation.py:130 SiluAndMul) --------------
+ * sgl_amd_dense_tiled_gemm's arguments followed by the scale arguments of sgl_amd_wstream_gemm_fp8, and that entry's
+ * arithmetic: y = bf16((x . f(w8)^T) * s + bias), x bf16, w8 OCP e4m3 [N, K] (w_row_stride in bytes, a multiple of 16), f the
+ * exact widening to bf16, bf16 MFMA with fp32 accumulation, activations never quantised.  scale_mode 0: w_scale[1]; 1:
+ * w_scale[N]; 2: w_scale[ceil(N / 128), scale_row_stride >= K / 128] (every 128-wide K chunk is scaled as it is folded into the
+ * running sum).  M >= 1 (the grid walks ceil(M / 256) row blocks), N %% 16 == 0, K %% 128 == 0.  block_n: 256 (three LDS stages)
+ * or 128 (four; the only form of scale_mode 2).  num_k_splits > 1 (M <= 65535): scaled fp32 partials [splits, M, N] in
+ * ws_partials (sgl_amd_dense_tiled_gemm_fp8_workspace_floats), summed in split order by the combine kernels of
+ * sgl_amd_wstream_gemm.  Epilogues as sgl_amd_dense_tiled_gemm; the scale meets the accumulator before either. */
+int sgl_amd_dense_tiled_gemm_fp8(const void* x, const void* w, const void* bias, void* y, int64_t M, int64_t N, int64_t K,
+                                 int64_t x_row_stride, int64_t w_row_stride, int64_t y_row_stride, int epilogue, int block_n,
+                                 int num_k_splits, void* ws_partials, void* stream, const float* w_scale, int scale_mode,
+                                 int64_t scale_row_stride);
+int64_t sgl_amd_dense_tiled_gemm_fp8_workspace_floats(int64_t M, int64_t N, int num_k_splits);
+
 #ifdef __cplusplus
 }
 #endif

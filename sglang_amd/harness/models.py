@@ -101,7 +101,8 @@ class Linear(nn.Module):
     """y = x W^T (+ b), W [out, in] bf16.  Decode batches (M <= 64) stream the weights through the
     gfx950 wstream GEMM; prefill-sized M uses hipBLASLt via torch (a plain library GEMM).
     weight_dtype="fp8_e4m3": W is stored as e4m3 + a per-output-channel fp32 `weight_scale` (kernels.quantize_fp8_weight,
-    weight-only: y = (x W8^T) * scale + b) and decode batches stream it through the fp8 wstream GEMM."""
+    weight-only: y = (x W8^T) * scale + b); decode batches stream it through the fp8 wstream GEMM, more rows than that takes
+    go to the fp8-weight MFMA tile GEMM (kernels.dense_tiled_gemm with w_scale)."""
 
     def __init__(self, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, weight_dtype: str = "auto"):
         super().__init__()
@@ -128,19 +129,27 @@ class Linear(nn.Module):
         if self.streams(x):
             return kernels.wstream_gemm(x, self.weight.data, self.bias.data if self.bias is not None else None, w_scale=self._scale)
         if self.weight_scale is not None:
+            if self.tiles_fp8(x):
+                return kernels.dense_tiled_gemm(x, self.weight.data, self.bias.data if self.bias is not None else None, w_scale=self._scale)
             return self._forward_fp8_rows(x)
         if self.tiles(x):
             return kernels.dense_tiled_gemm(x, self.weight.data, self.bias.data if self.bias is not None else None)
         return F.linear(kernels.unblock(x), self.weight, self.bias)
 
     def _forward_fp8_rows(self, x: torch.Tensor) -> torch.Tensor:
-        """More rows than the weight stream takes (prefill) over fp8 weights: widen the weight to bf16 (exact), a plain F.linear,
-        the scale and the bias in fp32, one rounding to bf16.  Harness plumbing, not a hot path: a prefill-sized fp8 GEMM is
-        not part of this package yet."""
+        """The fallback of tiles_fp8() (CPU tensors, odd strides or dtypes, more rows than were measured ahead) over fp8 weights: widen the weight to bf16 (exact), a
+        plain F.linear, the scale and the bias in fp32, one rounding to bf16.  Harness plumbing, not a hot path."""
         y = F.linear(kernels.unblock(x), self.weight.to(BF)).float() * self.weight_scale
         if self.bias is not None:
             y = y + self.bias.float()
         return y.to(BF)
+
+    def tiles_fp8(self, x: torch.Tensor) -> bool:
+        """Row-major bf16 rows on the GPU over fp8 weights, beyond what the weight stream takes: the fp8-weight MFMA tile GEMM, up
+        to the rows where it measured ahead of _forward_fp8_rows (kernels.DENSE_TILED_FP8_ROUTED_MAX_ROWS)."""
+        return (self.weight_scale is not None and x.is_cuda and x.dim() == 2 and x.stride(1) == 1 and x.dtype == BF
+                and x.stride(0) % 8 == 0 and x.data_ptr() % 16 == 0
+                and kernels.dense_tiled_fp8_preferred(x.shape[0], self.weight.shape[0], self.weight.shape[1]))
 
     def tiles(self, x: torch.Tensor, fused_silu: bool = False) -> bool:
         """129..512 row-major rows where the dense MFMA tile GEMM measured ahead of the library."""
@@ -195,6 +204,9 @@ class LlamaMLP(nn.Module):
         if (not OPERATOR_SURFACE_ONLY and self.gate_up_proj.bias is None and self.gate_up_proj.weight_scale is None
                 and self.gate_up_proj.tiles(x, fused_silu=True)):
             return kernels.dense_tiled_gemm(x, self.gate_up_proj.weight.data, epilogue="silu_and_mul")
+        if (not OPERATOR_SURFACE_ONLY and self.gate_up_proj.bias is None and self.gate_up_proj.tiles_fp8(x)
+                and self.gate_up_proj.weight.shape[0] % 32 == 0):
+            return kernels.dense_tiled_gemm(x, self.gate_up_proj.weight.data, epilogue="silu_and_mul", w_scale=self.gate_up_proj._scale)
         return self.act_fn(self.gate_up_proj(x))
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:

@@ -1306,24 +1306,85 @@ def dense_tiled_preferred(M: int, N: int, K: int, fused_silu: bool = False) -> b
     return not fused_silu and dense_tiled_supported(M, N, K) and (M, N, K) in _DENSE_TILED_WINS
 
 
+_DENSE_TILED_FP8_BLOCKS = (256, 128)    # wide first: twice the products per LDS byte; block scales run on the 128-row tile only
+
+
+def dense_tiled_fp8_supported(M: int, N: int, K: int) -> bool:
+    """Shapes of the fp8-weight tile GEMM (dense_tiled_fp8_gemm.hip): any row count."""
+    return M >= 1 and N > 0 and N % 16 == 0 and K % 128 == 0 and K >= 128
+
+
+# profiles/dense_tiled_fp8_gemm_sweep.json: up to 2048 rows the kernel beat the path it replaces (widen + library GEMM + fp32
+# scale) at every measured shape, by 1.39x (70B/8 qkv at 2048 rows) to 4.9x; at 8192 rows three of ten shapes were slower by more
+# than the spreads (8B down 845 vs 813 us, 70B/8 qkv 214 vs 192, 70B/8 gate_up 976 vs 925).  Nothing between was measured, so
+# the models route up to here and keep the old path beyond.
+DENSE_TILED_FP8_ROUTED_MAX_ROWS = 2048
+
+
+def dense_tiled_fp8_preferred(M: int, N: int, K: int) -> bool:
+    """Routing policy on top of dense_tiled_fp8_supported(): the measured row range (see the constant above)."""
+    return dense_tiled_fp8_supported(M, N, K) and M <= DENSE_TILED_FP8_ROUTED_MAX_ROWS
+
+
+@functools.lru_cache(maxsize=None)
+def choose_dense_tiled_fp8_config(M: int, N: int, K: int, fused_silu: bool = False, block_scales: bool = False) -> Tuple[int, int]:
+    """(block_n, k_splits) of the fp8-weight tile GEMM (fused_silu: N counts the rows of w = 2 I; one split runs the silu in
+    the GEMM's epilogue, more go through the combine-silu kernel; block_scales: the 128-row tile is the only form).  The model
+    of choose_dense_tiled_config(): strips x row blocks x splits are paid for in whole rounds of the 256 CUs, a round costs
+    its K steps (fitted to the one-round and the many-round one-split rows of profiles/dense_tiled_fp8_gemm_sweep.json: 8B o at
+    2048 rows, 69.5 us = ~16.5 ns per K element for the 256 x 128 tile; 8B gate_up at 8192 rows, 1703 us over 14 rounds = ~29.7 ns
+    for the 256 x 256 one), the walk never beats the weight bytes over ~5.5 TB/s, and split-K pays the fp32 partial round trip
+    plus the combine launch (the figures of choose_wstream_config); it is bounded by the K chunks, by 16 and by the 65535 rows
+    the combine kernels take."""
+    row_blocks = (M + _DENSE_TILED_ROW_BLOCK - 1) // _DENSE_TILED_ROW_BLOCK
+    chunks = K // 128
+    max_splits = 1 if M > 65535 else min(chunks, 16)
+    best = None
+    for s in range(1, max_splits + 1):
+        for bn in ((128,) if block_scales else _DENSE_TILED_FP8_BLOCKS):
+            strips = (N // 2 + bn // 2 - 1) // (bn // 2) if (fused_silu and s == 1) else (N + bn - 1) // bn
+            rounds = (strips * row_blocks * s + _NUM_CUS - 1) // _NUM_CUS
+            steps = (chunks + s - 1) // s * 128
+            t = 2.0e-6 + max(rounds * steps * (29.7e-9 if bn == 256 else 16.5e-9), N * K / 5.5e12)
+            if s > 1:
+                t += 2 * s * M * N * 4 / 4e12 + 2.5e-6
+            if best is None or t < best[0]:
+                best = (t, bn, s)
+    return best[1], best[2]
+
+
 def dense_tiled_gemm(x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, epilogue: str = "none",
                      out: Optional[torch.Tensor] = None, block_n: Optional[int] = None,
-                     splits: Optional[int] = None) -> torch.Tensor:
+                     splits: Optional[int] = None, w_scale: Optional[torch.Tensor] = None) -> torch.Tensor:
     """F.linear(x, w, bias) for 129..512 rows on the dense MFMA tile kernel; epilogue="silu_and_mul": w is [2 I, K]
     (gate rows, then up rows) and the result is silu(gate) * up [M, I] (in the GEMM's own epilogue with one split,
-    in the split-K combine kernel otherwise).  x and out are row-major with any aligned row stride."""
+    in the split-K combine kernel otherwise).  x and out are row-major with any aligned row stride.
+    w may be torch.float8_e4m3fn with fp32 `w_scale` of shape () / (1,), (N,) or (ceil(N/128), K/128): weight-only fp8
+    (dense_tiled_fp8_gemm.hip), the linear being (x . w^T) * scale in fp32 as in wstream_gemm, for ANY row count;
+    block_n is then 256 or 128 (128 with block scales)."""
     _dev(x, w)
-    _need(x.dtype == _BF16 and w.dtype == _BF16 and x.dim() == 2 and w.dim() == 2, "dense_tiled_gemm: bf16 2-D x / w")
+    _need(x.dtype == _BF16 and w.dtype in (_BF16, _E4M3) + _FP8_OTHERS and x.dim() == 2 and w.dim() == 2,
+          f"dense_tiled_gemm: bf16 2-D x, 2-D bf16 or float8_e4m3fn w (got {w.dtype})")
     _need(epilogue in ("none", "silu_and_mul"), "dense_tiled_gemm: epilogue is 'none' or 'silu_and_mul'")
     M, K = x.shape
     N = w.shape[0]
     _need(w.shape[1] == K and x.stride(1) == 1 and w.stride(1) == 1, "dense_tiled_gemm: shapes / contiguity")
     _need(bias is None or (bias.dtype == _BF16 and bias.shape == (N,) and bias.is_contiguous()), "dense_tiled_gemm: bias is bf16 [N]")
+    scale_args = _fp8_scale_args("dense_tiled_gemm", w, w_scale, N, K)
     ep = _WS_EPILOGUES[epilogue]
     n_out = N // 2 if ep == 1 else N
     if out is None:
         out = torch.empty((M, n_out), dtype=_BF16, device=x.device)
     _need(out.dtype == _BF16 and out.shape == (M, n_out) and out.stride(1) == 1, "dense_tiled_gemm: out is bf16 [M, N] rows")
+    if scale_args:
+        if block_n is None or splits is None:
+            bn_auto, s_auto = choose_dense_tiled_fp8_config(M, N, K, ep == 1, scale_args[1] == 2)
+        bn = block_n or bn_auto
+        s = splits or s_auto
+        ws = _gemm_workspace(x.device, native.lib().sgl_amd_dense_tiled_gemm_fp8_workspace_floats(M, N, s)) if s > 1 else None
+        native.call("sgl_amd_dense_tiled_gemm_fp8", x.data_ptr(), w.data_ptr(), _ptr(bias), out.data_ptr(), M, N, K, x.stride(0),
+                    w.stride(0), out.stride(0), ep, bn, s, _ptr(ws), _stream(), *scale_args)
+        return out
     if block_n is None or splits is None:
         bn_auto, s_auto = choose_dense_tiled_config(M, N, K, ep == 1 and splits in (None, 1))
     bn = block_n or bn_auto
